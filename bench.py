@@ -25,10 +25,18 @@ Workloads:
             order, so a trace arrives as several runs): unpack + the SAMPLE
             stage, which takes the sort-based path.
 
+A plain run sets up, warms up, times the steps and prints the result line
+(metric, value, ms_per_step, the per-kernel HIP-event times the timed steps
+collected).  --dump-outputs DIR also writes what the last timed step left in
+the caller's output buffers (dump_outputs below).  Everything else runs only
+with --full:
+
 The CPU baseline (rank 0, N = 1) is the oracle (oracle/*.c, built with
 -march=native on this host) on C1 = 1M spans of the fused mix, seed
 0x0D160001, on this process's CPU share; the same oracle
-then checks the timed GPU output at full size (parity_vs_oracle).
+then checks the timed GPU output at full size (parity_vs_oracle).  --full
+also adds the roofline figures (algorithmic bytes, PMC traffic, the measured
+stream-copy bandwidth).
 """
 from __future__ import annotations
 
@@ -333,6 +341,70 @@ def build_owner_batch(eng, wl, threads):
     return recv, recv.numel() // rb, spans_repr, rb
 
 
+# ---- --dump-outputs -------------------------------------------------------------------
+DUMP_SEED = 0x0D16D0          # the span sample is the same for every run of one configuration
+DUMP_SPANS = 1 << 19          # sampled spans (20 B each on disk)
+DUMP_TMPL_BYTES = 6 << 20     # template bytes of the sample's leading spans (4 B each on disk)
+DUMP_ATTRSETS = 1 << 18       # leading attribute-set counters (8 B each on disk)
+
+
+def _dump_sample(n, share):
+    """Sorted span indices: all of them, or a seeded draw of about
+    DUMP_SPANS / share of a larger batch (duplicates dropped)."""
+    want = max(DUMP_SPANS // share, 1)
+    if n <= want:
+        return np.arange(n, dtype=np.int64)
+    return np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, want, dtype=np.int64))
+
+
+def dump_outputs(dirpath, batches, stages, share=1):
+    """Writes what the last timed step left in the caller's output buffers as
+    <dirpath>/<prefix><name>.npy (float32; float64 where a value can pass 2^24),
+    under 48 MB in all.  batches: (prefix, outputs, n_spans, n_attrsets), where
+    outputs maps names to the device tensors a caller of ose_process_device (or
+    of ose_shard_decide: only "keep") handed in.  Per sampled span: its index,
+    keep, url_out and the length of its template (0 where url_out is 0); the
+    template bytes of the sample's leading spans, which the refs name (so two
+    builds compare whatever the arena's layout); the attribute-set byte
+    counters and accepted_spans, which every warm-up and timed call added to."""
+    import torch
+
+    from odigos_amd import native
+    d = Path(dirpath)
+    d.mkdir(parents=True, exist_ok=True)
+    for prefix, o, n, n_attrsets in batches:
+        idx = _dump_sample(n, share)
+        idx_t = torch.from_numpy(idx).cuda()
+        res = {"span_index": idx.astype(np.float64)}
+        if stages & native.STAGE_SAMPLE:
+            res["keep"] = o["keep"][:n][idx_t].cpu().numpy().astype(np.float32)
+        if stages & native.STAGE_TEMPLATE:
+            url_out = o["url_out"][:n][idx_t]
+            res["url_out"] = url_out.cpu().numpy().astype(np.float32)
+            refs = o["tmpl"][: 8 * n].view(torch.int32).view(n, 2)[idx_t].to(torch.int64) & 0xFFFFFFFF
+            lens = torch.where(url_out != 0, refs[:, 1], torch.zeros_like(refs[:, 1]))
+            res["tmpl_len"] = lens.cpu().numpy().astype(np.float32)
+            ends = torch.cumsum(lens, 0)
+            k = int(torch.searchsorted(ends, torch.tensor([DUMP_TMPL_BYTES // share], device=ends.device),
+                                       right=True).item())
+            lens, ends, offs = lens[:k], ends[:k], refs[:k, 0]
+            total = int(ends[-1].item()) if k else 0
+            if total:
+                flat = torch.repeat_interleave(offs - (ends - lens), lens) + torch.arange(total, device=ends.device)
+                arena = o["tmpl_arena"]
+                if int(flat.max().item()) >= arena.numel():
+                    raise SystemExit("a template ref points past the template arena")
+                res["tmpl_bytes"] = arena[flat].cpu().numpy().astype(np.float32)
+            else:
+                res["tmpl_bytes"] = np.zeros(0, dtype=np.float32)
+        if stages & native.STAGE_SIZE:
+            a = min(n_attrsets, max(DUMP_ATTRSETS // share, 1))
+            res["attrset_bytes"] = o["attrset_bytes"][: 8 * a].cpu().numpy().view(np.int64).astype(np.float64)
+            res["accepted_spans"] = o["accepted_spans"][:8].cpu().numpy().view(np.int64).astype(np.float64)
+        for name, arr in res.items():
+            np.save(d / f"{prefix}{name}.npy", arr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -342,8 +414,13 @@ def main():
     # multi-GPU runs exercise (trace-id exchange when N > 1); DESIGN.md §6
     ap.add_argument("--workload", default="fused", choices=sorted(WORKLOADS))
     ap.add_argument("--spans", type=int, default=0, help="override the workload's span count")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the CPU baseline, the oracle parity check of the whole "
+                         "timed batch and the roofline figures")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (a seeded sample of them) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: leave the parity check out")
     # refs (OSE_STAGE_TEMPLATE_REFS): the templates stay where the GPU assembled
     # them and the device-resident consumer follows the refs; packed: the
     # compact arena a host copy needs (one more pass over the template bytes)
@@ -488,7 +565,15 @@ def main():
         status = int(d.out_numpy("device_status", np.uint32)[0])
         if status:
             raise SystemExit(f"device status {status}: kernel reported a failure")
-    units = torch.tensor([float(n_units)], dtype=torch.float64, device="cuda")
+    if args.dump_outputs:
+        if args.workload == "node8":
+            batches = [(f"rank{r}_", d.o, g.cols.n_spans, g.cols.n_attrsets) for r, (g, d) in enumerate(zip(gens, dbs))]
+        elif args.workload == "owner":
+            batches = [("", {"keep": ex._ensure(n_rec)["keep"]}, n_rec, 0)]   # the buffer the timed calls wrote
+        else:
+            batches = [(f"rank{rank}_" if world > 1 else "", db.o, n_units, gen.cols.n_attrsets)]
+        dump_outputs(args.dump_outputs, batches, stages, share=max(world, len(batches)))
+    units =torch.tensor([float(n_units)], dtype=torch.float64, device="cuda")
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -522,23 +607,21 @@ def main():
                       "projected_ms_per_gpu_step": elapsed / args.steps * 1e3 / W,
                       "projected_xgmi_ms": native.XREC_BYTES * max(x[0] for x in st_) * (W - 1) / W /
                                            (7 * 153e9) * 1e3 * 2})   # records + keep bytes back, 7 links of 153 GB/s
-    if args.workload == "owner":
-        b_alg = None
-        achieved = 0.0
-    else:
-        if args.workload == "node8":
-            # per-GPU algorithmic bytes over the projected per-GPU step (wall / 8)
-            b_alg = sum(algorithmic_bytes(wl, g, d, g.cols.n_spans, cfg) for g, d in zip(gens, dbs))
+    b_alg = None
+    achieved = 0.0
+    if args.full and args.workload == "node8":
+        # per-GPU algorithmic bytes over the projected per-GPU step (wall / 8)
+        b_alg = sum(algorithmic_bytes(wl, g, d, g.cols.n_spans, cfg) for g, d in zip(gens, dbs))
+        achieved = b_alg / (elapsed / args.steps) / 1e9
+    elif args.full and args.workload != "owner":
+        b_alg = algorithmic_bytes(wl, gen, db, n_units, cfg)
+        achieved = b_alg / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
+        if overlapped:   # the brackets overlap: the stage set's GPU time is at most the step
             achieved = b_alg / (elapsed / args.steps) / 1e9
-        else:
-            b_alg = algorithmic_bytes(wl, gen, db, n_units, cfg)
-            achieved = b_alg / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
-            if overlapped:   # the brackets overlap: the stage set's GPU time is at most the step
-                achieved = b_alg / (elapsed / args.steps) / 1e9
 
     traffic = None
     tj = Path(args.traffic_json)
-    if tj.exists():
+    if args.full and tj.exists():
         try:
             d = json.loads(tj.read_text())
             ent = d.get(args.workload, {}).get(kname)
@@ -567,30 +650,34 @@ def main():
                    "parallelism": (f"dp{world}: trace-id all-to-all (RCCL) of sampling partials, local templating/size"
                                    if world > 1 and stages & native.STAGE_SAMPLE else
                                    f"dp{world}: independent span shards, no data-path collective"), **extra},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                     "kernel": kname, "kernel_ms": None if args.workload == "node8" else k_ms,
-                     "time_base": "step (SAMPLE and the URL planning overlap on two streams; kernel_ms_each are "
-                                  "overlapping brackets)" if overlapped else "kernel_ms",
-                     "kernel_ms_each": None if args.workload == "node8" else per_k,
-                     "algorithmic_bytes_per_launch": b_alg},
     }
-    # measured HBM stream-copy bandwidth beside the spec peak (2 x 2 GiB copy,
-    # read + written bytes over the kernel time)
-    try:
-        import ctypes as C
-        a_ = torch.empty(2 << 30, dtype=torch.uint8, device="cuda")
-        b_ = torch.empty_like(a_)
-        bw = C.c_double()
-        native.check(native.lib().osehost_stream_copy(b_.data_ptr(), a_.data_ptr(), a_.numel(), 10, C.c_void_p(sh),
-                                                      C.byref(bw)))
-        out["roofline"]["stream_copy_gbs"] = bw.value
-        out["roofline"]["frac_of_stream_copy"] = achieved / bw.value if bw.value else None
-        del a_, b_
-    except Exception as ex:   # diagnostics only
-        out["roofline"]["stream_copy_gbs"] = None
-        print("stream copy measurement failed:", ex, file=sys.stderr)
-    if world > 1 and not args.no_parity:
+    if not args.full:
+        # the HIP-event brackets the timed steps recorded (device ms per step)
+        out["kernel_ms_each"] = None if args.workload == "node8" else per_k
+    else:
+        out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                           "kernel": kname, "kernel_ms": None if args.workload == "node8" else k_ms,
+                           "time_base": "step (SAMPLE and the URL planning overlap on two streams; kernel_ms_each "
+                                        "are overlapping brackets)" if overlapped else "kernel_ms",
+                           "kernel_ms_each": None if args.workload == "node8" else per_k,
+                           "algorithmic_bytes_per_launch": b_alg}
+        # measured HBM stream-copy bandwidth beside the spec peak (2 x 2 GiB copy,
+        # read + written bytes over the kernel time)
+        try:
+            import ctypes as C
+            a_ = torch.empty(2 << 30, dtype=torch.uint8, device="cuda")
+            b_ = torch.empty_like(a_)
+            bw = C.c_double()
+            native.check(native.lib().osehost_stream_copy(b_.data_ptr(), a_.data_ptr(), a_.numel(), 10,
+                                                          C.c_void_p(sh), C.byref(bw)))
+            out["roofline"]["stream_copy_gbs"] = bw.value
+            out["roofline"]["frac_of_stream_copy"] = achieved / bw.value if bw.value else None
+            del a_, b_
+        except Exception as e:   # diagnostics only
+            out["roofline"]["stream_copy_gbs"] = None
+            print("stream copy measurement failed:", e, file=sys.stderr)
+    if args.full and world > 1 and not args.no_parity:
         # every rank's outputs against the oracle: split workloads (C4) on rank 0
         # over the W sources concatenated in rank order (the global batch the
         # trace-id exchange decides), per-GPU workloads on each rank's own batch
@@ -625,7 +712,7 @@ def main():
         if rank == 0:
             out["parity_vs_oracle"] = all(par.values())
             out["parity"] = par
-    if rank == 0 and world == 1 and args.workload != "owner":
+    if args.full and rank == 0 and world == 1 and args.workload != "owner":
         orc = native_oracle()
         if not args.no_cpu_baseline:
             mt, st1, sample = cpu_baseline(wl, cfg, stages, share)
