@@ -180,6 +180,7 @@ Engine::~Engine() {
     if (w->dup_ready) (void)hipEventDestroy(w->dup_ready);
     if (w->fork) (void)hipEventDestroy(w->fork);
     if (w->join) (void)hipEventDestroy(w->join);
+    if (w->join2) (void)hipEventDestroy(w->join2);
     delete w;
   }
 }
@@ -265,6 +266,9 @@ void Engine::release_ws(Workspace* w, hipStream_t st) {
   std::lock_guard<std::mutex> g(mu);
   free_ws.push_back(w);
 }
+#ifndef OSE_SIDE_STREAM_PRIO
+#define OSE_SIDE_STREAM_PRIO 0
+#endif
 hipStream_t Engine::take_stream() {
   std::lock_guard<std::mutex> g(mu);
   if (!free_streams.empty()) {
@@ -273,7 +277,13 @@ hipStream_t Engine::take_stream() {
     return s;
   }
   hipStream_t s = nullptr;
+#if OSE_SIDE_STREAM_PRIO   // A/B: the pool's streams at the greatest priority (profiles/tail_parts_ab.txt)
+  int least = 0, greatest = 0;
+  (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
+  if (hipStreamCreateWithPriority(&s, hipStreamNonBlocking, greatest) != hipSuccess) return nullptr;
+#else
   if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return nullptr;
+#endif
   streams.push_back(s);
   return s;
 }
@@ -347,9 +357,11 @@ int run_url_back(Engine* e, const UrlKernelArgs& a, hipStream_t st);
 // SAMPLE stage's scratch whose slow path is still to be queued).  front: only
 // plan, plan_slow, scan and emit_slow are queued, and the arguments of the
 // rest go to *front (run_url_back queues url_copy, fused with
-// odigostrafficmetrics' spans pass when front->fuse_size is set).
+// odigostrafficmetrics' spans pass when front->fuse_size is set).  planned:
+// an event recorded on st behind url_plan_slow_kernel, when every span's
+// plan_len and url_out are written (all the refs form's spans pass reads).
 int run_url(Engine* e, const ose_columns* c, const ose_outputs* o, hipStream_t st, Workspace* ws, size_t ws_off = 0,
-            UrlKernelArgs* front = nullptr, bool refs = false, uint32_t grid_mult = 1) {
+            UrlKernelArgs* front = nullptr, bool refs = false, uint32_t grid_mult = 1, hipEvent_t planned = nullptr) {
   if (!e->has_url) return fail(OSE_EINVAL, "odigosurltemplate is not configured on this engine");
   if (!c->url_flags || !c->kind || !c->path || !c->arena || !o->url_out || !o->tmpl || !o->tmpl_arena)
     return fail(OSE_EINVAL, "TEMPLATE stage needs url_flags, kind, path, arena, url_out, tmpl, tmpl_arena");
@@ -431,6 +443,7 @@ int run_url(Engine* e, const ose_columns* c, const ose_outputs* o, hipStream_t s
   if (front) *front = a;
   if (n == 0) {
     if (o->tmpl_arena_used) HIP_TRY(hipMemsetAsync(o->tmpl_arena_used, 0, 8, st));
+    if (planned) HIP_TRY(hipEventRecord(planned, st));
     return 0;
   }
   if (a.ablate & 512) {   // diagnostics: per-section shader clocks (tools/url_clocks.py)
@@ -446,6 +459,7 @@ int run_url(Engine* e, const ose_columns* c, const ose_outputs* o, hipStream_t s
   launch_url_plan_slow(a, st);
   HIP_TRY(hipGetLastError());
   e->prof_end(tm, st);
+  if (planned) HIP_TRY(hipEventRecord(planned, st));
   e->prof_begin("url_scan_kernel", st, tm);
   launch_url_scan(a, st);
   HIP_TRY(hipGetLastError());
@@ -467,11 +481,15 @@ int run_url(Engine* e, const ose_columns* c, const ose_outputs* o, hipStream_t s
 
 int run_url_back(Engine* e, const UrlKernelArgs& a, hipStream_t st) {
   if (a.n_spans == 0) return 0;
-  Engine::Timed tm{};
-  e->prof_begin("url_copy_kernel", st, tm);
-  launch_url_copy(a, st);
-  HIP_TRY(hipGetLastError());
-  e->prof_end(tm, st);
+  // refs form: every span's ref is written by the kernel that placed its
+  // group, so url_copy_kernel runs only as the fused spans pass
+  if (!a.refs || a.fuse_size) {
+    Engine::Timed tm{};
+    e->prof_begin("url_copy_kernel", st, tm);
+    launch_url_copy(a, st);
+    HIP_TRY(hipGetLastError());
+    e->prof_end(tm, st);
+  }
   if (a.ablate & 512) {
     uint64_t h[16];
     uint32_t cnt[4];
@@ -531,6 +549,14 @@ int run_stages(Engine* e, const ose_columns* c, const ose_outputs* o, uint32_t m
   //   url_off   the URL stage's scratch
   //   size_off  the size stage's sums (after the URL scratch: with TEMPLATE
   //             its spans pass runs inside url_copy_kernel)
+  // The size scratch's per-scope sums are cleared by prepare_size, after the
+  // join.  With the URL front forked nothing queued earlier touches the bytes
+  // from size_off on (url_off lies past the whole trace scratch, size_off
+  // past the URL scratch), so the clear could be queued ahead of the trace
+  // stage; measured, that fill is starved beside url_plan_kernel (218 us
+  // instead of 27), delays trace_eval_kernel behind it and costs the C4
+  // step 0.06 ms (profiles/tail_parts_ab.txt).  Everywhere else the size
+  // scratch overlaps an earlier stage's (SAMPLE | SIZE: size_off = 256).
   size_t need = 0;
   if (mask & OSE_STAGE_SAMPLE) need = sampling_scratch_bytes(n);
   const size_t url_off = (mask & OSE_STAGE_SAMPLE) ? align_up(defer ? sampling_scratch_bytes(n) : 256, 256) : 0;
@@ -570,9 +596,10 @@ int run_stages(Engine* e, const ose_columns* c, const ose_outputs* o, uint32_t m
   if (!one_stream && !rc && defer && n >= kForkSpans) {
     if (!ws->fork) (void)hipEventCreateWithFlags(&ws->fork, hipEventDisableTiming);
     if (!ws->join) (void)hipEventCreateWithFlags(&ws->join, hipEventDisableTiming);
+    if (!ws->join2) (void)hipEventCreateWithFlags(&ws->join2, hipEventDisableTiming);
     // (the fork stream's priority, high or low, measured no different:
     // profiles/r6u_url_stream_priority_ab.txt)
-    if (ws->fork && ws->join) ust = e->take_stream();
+    if (ws->fork && ws->join && ws->join2) ust = e->take_stream();
     if (ust && (hipEventRecord(ws->fork, st) != hipSuccess || hipStreamWaitEvent(ust, ws->fork, 0) != hipSuccess)) {
       e->give_stream(ust);
       ust = nullptr;
@@ -580,8 +607,23 @@ int run_stages(Engine* e, const ose_columns* c, const ose_outputs* o, uint32_t m
   }
   const bool tmpl = !rc && (mask & OSE_STAGE_TEMPLATE);
   ws->beside_url = ust && tmpl;
-  if (ust && tmpl)
-    rc = run_url(e, c, o, ust, ws, url_off, &ua, (mask & OSE_STAGE_TEMPLATE_REFS) != 0, url_plan_grid_mult(plan_groups, true));
+  // refs form with the fused spans pass: the copy / size launches need only
+  // what url_plan_kernel and url_plan_slow_kernel wrote, so the join event is
+  // recorded behind those two and url_scan_kernel / url_emit_slow_kernel run
+  // on the side stream beside url_copy_kernel / size_tail_kernel; the side
+  // stream is joined a second time at the end of the call
+  bool early_join = false;
+#ifndef OSE_URL_JOIN_LATE
+  early_join = ust && tmpl && !rc && (mask & OSE_STAGE_TEMPLATE_REFS) && (mask & OSE_STAGE_SIZE) &&
+               !(OSE_DIAG && getenv("OSE_NO_FUSED_SIZE"));
+#endif
+  bool join_recorded = false;
+  if (ust && tmpl && !rc) {
+    rc = run_url(e, c, o, ust, ws, url_off, &ua, (mask & OSE_STAGE_TEMPLATE_REFS) != 0, url_plan_grid_mult(plan_groups, true),
+                 early_join ? ws->join : nullptr);
+    // (an error before the record leaves the join to the usual place)
+    join_recorded = early_join && !rc;
+  }
   // gateway pipeline order: odigossampling (-24) before odigosurltemplate (1)
   if (!rc && (mask & OSE_STAGE_SAMPLE)) rc = run_sampling(e, c, o, group_mode, rnd, st, ws, gate_on_host ? &sample_tail : nullptr);
   if (sample_tail && !defer) {
@@ -595,13 +637,12 @@ int run_stages(Engine* e, const ose_columns* c, const ose_outputs* o, uint32_t m
     if (!rc) rc = trc;
   }
   if (ust) {   // join: everything below runs on the caller's stream after both
-    const hipError_t je = hipEventRecord(ws->join, ust);
+    const hipError_t je = join_recorded ? hipSuccess : hipEventRecord(ws->join, ust);
     const hipError_t jw = je == hipSuccess ? hipStreamWaitEvent(st, ws->join, 0) : je;
     if (jw != hipSuccess) {   // cannot order the streams: wait for the URL work on the host
       (void)hipStreamSynchronize(ust);
       if (!rc) rc = fail(OSE_EDEVICE, std::string("URL stream join: ") + hipGetErrorString(jw));
     }
-    e->give_stream(ust);
   }
   // odigostrafficmetrics runs last, on what the earlier stages left (the
   // decisions are final here: SAMPLE's tail has been queued)
@@ -620,6 +661,20 @@ int run_stages(Engine* e, const ose_columns* c, const ose_outputs* o, uint32_t m
     rc = run_url_back(e, ua, st);
   }
   if (!rc && size_on) rc = run_size_tail(e, sa, st);
+  if (ust) {
+    if (join_recorded) {
+      // second join: the side stream's scan and slow emit end before the
+      // caller's stream goes on, the workspace is released and the side
+      // stream is handed back
+      const hipError_t je = hipEventRecord(ws->join2, ust);
+      const hipError_t jw = je == hipSuccess ? hipStreamWaitEvent(st, ws->join2, 0) : je;
+      if (jw != hipSuccess) {
+        (void)hipStreamSynchronize(ust);
+        if (!rc) rc = fail(OSE_EDEVICE, std::string("URL stream join: ") + hipGetErrorString(jw));
+      }
+    }
+    e->give_stream(ust);
+  }
   ws->beside_url = false;
   e->release_ws(ws, st);
   return rc;

@@ -99,7 +99,7 @@ struct Workspace {
   hipEvent_t dup_ready = nullptr;
   // SAMPLE + TEMPLATE: the URL planning kernels run on a second stream
   // beside the trace stage (run_stages): fork and join events
-  hipEvent_t fork = nullptr, join = nullptr;
+  hipEvent_t fork = nullptr, join = nullptr, join2 = nullptr;
   bool beside_url = false;   // this call's trace stage runs beside the forked URL planning
 };
 

@@ -1670,13 +1670,19 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
         a.group_scr[g] = region + scr_used;
       }
       // refs form: the image stays where it is, so the group's template refs
-      // are known here (url_copy_kernel writes only the other groups')
+      // are known here
       if (a.refs && i < a.n_spans) a.tmpl[i] = ose_strref{(uint32_t)(region + scr_used + local), p.len};
       scr_used += need;
-    } else if (lane == 0) {
-      a.group_sum[g] = sum;
-      a.group_scr[g] = ~0ull;
-      if (sum) a.slow_groups[atomicAdd(a.slow_count, 1u)] = g;
+    } else {
+      // refs form: a group without output bytes is listed nowhere, so its
+      // (empty) refs are written here; url_emit_slow_kernel writes the refs
+      // of the groups it is handed
+      if (a.refs && sum == 0 && i < a.n_spans) a.tmpl[i] = ose_strref{0, 0};
+      if (lane == 0) {
+        a.group_sum[g] = sum;
+        a.group_scr[g] = ~0ull;
+        if (sum) a.slow_groups[atomicAdd(a.slow_count, 1u)] = g;
+      }
     }
     }
     if (tm) { const uint64_t t1 = clk(); t_emit += t1 - t0; t0 = t1; }
@@ -1787,6 +1793,13 @@ __device__ __forceinline__ CopyCols copy_cols(const UrlKernelArgs& a, uint32_t g
   if (i < a.n_spans) c.len = a.plan_len[i];
   return c;
 }
+// refs form: only the span's plan length (the spans pass's template length)
+__device__ __forceinline__ CopyCols copy_len(const UrlKernelArgs& a, uint32_t g, int lane) {
+  CopyCols c{0, 0, 0, ~0ull};
+  const uint64_t i = (uint64_t)g * kWave + lane;
+  if (i < a.n_spans) c.len = a.plan_len[i];
+  return c;
+}
 // one destination round (up to 64 chunks of 16 bytes) of a group's image: v
 // holds scratch chunk c = c0 + lane
 __device__ __forceinline__ void copy_round(uint8_t* gdst, uint32_t shift, uint64_t endb, uint32_t c0, uint32_t nchunk,
@@ -1828,7 +1841,7 @@ struct CopyJob {
 };
 __device__ __forceinline__ CopyJob copy_job(const UrlKernelArgs& a, const CopyCols& c) {
   CopyJob j{};
-  j.on = !a.refs && c.so != ~0ull && c.gsum != 0 && c.base + c.gsum <= a.out_cap;
+  j.on = c.so != ~0ull && c.gsum != 0 && c.base + c.gsum <= a.out_cap;
   if (!j.on) return j;
   j.src = reinterpret_cast<const uint4*>(a.scratch + c.so);
   j.shift = (uint32_t)(c.base & 3);
@@ -1858,37 +1871,25 @@ __device__ __forceinline__ void copy_rest(const CopyJob& j, uint4 v, uint32_t& c
 // loaded with the group's copy columns, so the pass adds no round trip and no
 // second walk over the spans (size_span_kernel is then not launched); the
 // surviving spans are counted per block into size_partials.
-template <bool kSize>
+// kRefs (with kSize only): the refs form.  Every kernel that decides a
+// group's place writes its refs there (url_plan_kernel, url_plan_slow_kernel,
+// url_emit_slow_kernel) and no image moves, so this kernel is the spans pass
+// alone: the plan lengths and the span columns, no group columns, no length
+// scan; without the size pass it is not launched at all in the refs form.
+template <bool kSize, bool kRefs>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(kSize ? 5 : 6, 8))) void url_copy_kernel(UrlKernelArgs a) {
+  static_assert(kSize || !kRefs, "the refs form has no copy pass");
   const int lane = threadIdx.x & 63;
   const uint32_t stride = wave_stride();
-  if (!kSize && a.refs) {
-    // refs form without the size pass: url_plan_kernel wrote the refs of the
-    // groups it assembled; a wave looks at 64 groups' image offsets at once
-    // and writes the refs of the others (their bytes are placed at the
-    // scanned group base by url_emit_slow_kernel)
-    for (uint64_t g0 = (uint64_t)wave_first_group() * kWave; g0 < a.n_groups; g0 += (uint64_t)stride * kWave) {
-      const uint64_t gg = g0 + lane;
-      const bool other = gg < a.n_groups && a.group_scr[gg] == ~0ull;
-      for (uint64_t m = __ballot(other); m; m &= m - 1) {
-        const uint32_t g = (uint32_t)(g0 + __builtin_ctzll(m));
-        const CopyCols A = copy_cols(a, g, lane);
-        uint32_t unused;
-        const uint32_t la = wave_excl_scan(A.len, &unused);
-        const uint64_t ia = (uint64_t)g * kWave + lane;
-        if (ia < a.n_spans) a.tmpl[ia] = ose_strref{(uint32_t)(A.base + la), A.len};
-      }
-    }
-    return;
-  }
   uint32_t kept = 0;
   const bool sz_on = kSize && !sizedev::size_batch_dropped(a.sz);
   uint32_t g = wave_first_group();
+  if (kRefs && !sz_on) g = a.n_groups;   // a dropped batch: nothing to count
   // the next group's columns are loaded while this group is worked on
   CopyCols An{0, 0, 0, ~0ull};
   sizedev::SpanCols xn{};
   if (g < a.n_groups) {
-    An = copy_cols(a, g, lane);
+    An = kRefs ? copy_len(a, g, lane) : copy_cols(a, g, lane);
     if (kSize && sz_on) xn = sizedev::size_span_load(a.sz, (uint64_t)g * kWave + lane, false);
   }
   for (; g < a.n_groups; g += stride) {
@@ -1897,26 +1898,25 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(kSize 
     const sizedev::SpanCols x0 = xn;
     const bool more = g + stride < a.n_groups;
     if (more) {
-      An = copy_cols(a, g + stride, lane);
+      An = kRefs ? copy_len(a, g + stride, lane) : copy_cols(a, g + stride, lane);
       if (kSize && sz_on) xn = sizedev::size_span_load(a.sz, (uint64_t)(g + stride) * kWave + lane, false);
     }
     sizedev::SpanCols x = x0;
-    uint32_t unused;
-    const uint32_t la = wave_excl_scan(A.len, &unused);
-    const CopyJob ja = copy_job(a, A);
-    const uint4 va = copy_load(ja, 0);
-    if (ia < a.n_spans && !(a.refs && A.so != ~0ull)) {
-      // refs mode: a fast group's template stays in its scratch image (its
-      // refs were written by url_plan_kernel)
-      const uint64_t at = a.refs && A.so != ~0ull ? A.so : A.base;
-      a.tmpl[ia] = ose_strref{(uint32_t)(at + la), A.len};
+    CopyJob ja{};
+    uint4 va = make_uint4(0, 0, 0, 0);
+    if (!kRefs) {
+      uint32_t unused;
+      const uint32_t la = wave_excl_scan(A.len, &unused);
+      ja = copy_job(a, A);
+      va = copy_load(ja, 0);
+      if (ia < a.n_spans) a.tmpl[ia] = ose_strref{(uint32_t)(A.base + la), A.len};
     }
     if (kSize && sz_on) {
       x.tl = A.len;
       kept += sizedev::size_span_finish(a.sz, x);
     }
     uint32_t carry = 0;
-    if (ja.on) copy_rest(ja, va, carry);
+    if (!kRefs && ja.on) copy_rest(ja, va, carry);
     if (!more) break;
   }
   if (kSize) {
@@ -2028,6 +2028,8 @@ __global__ __launch_bounds__(kWave) void url_plan_slow_kernel(UrlKernelArgs a) {
       a.plan_code[i] = p.code;
     }
     const uint64_t sum = wave_sum_u64(p.len);
+    // refs form: an empty group is listed nowhere, its refs are written here
+    if (a.refs && sum == 0 && i < a.n_spans) a.tmpl[i] = ose_strref{0, 0};
     if (lane == 0) {
       a.group_sum[g] = sum;
       a.group_scr[g] = ~0ull;
@@ -2067,10 +2069,13 @@ __global__ __launch_bounds__(kThreads) void url_emit_slow_kernel(UrlKernelArgs a
     const uint64_t i = (uint64_t)g * kWave + lane;
     const EmitCols c = emit_cols(a, g, lane);
     const uint64_t base = c.base, gtotal = c.gsum;
-    if (base + gtotal > a.out_cap) continue;   // overflow: the scan flagged it
     const uint32_t len = c.len, meta = c.meta, mode = meta & 7u;
     uint32_t unused;
     const uint32_t local = wave_excl_scan(len, &unused);
+    // refs form: this kernel writes the refs of the groups it places (also of
+    // one that overflows: every span's ref is written on every call)
+    if (a.refs && i < a.n_spans) a.tmpl[i] = ose_strref{(uint32_t)(base + local), len};
+    if (base + gtotal > a.out_cap) continue;   // overflow: the scan flagged it
     const bool needs_path = emit_needs_path(meta);
     const ose_strref pr = needs_path ? c.pr : ose_strref{0, 0};
     uint32_t nbytes;
@@ -2175,10 +2180,13 @@ uint32_t url_copy_blocks(uint32_t n_groups) {
 }
 void launch_url_copy(const UrlKernelArgs& a, hipStream_t st) {
   const uint32_t blocks = url_copy_blocks(a.n_groups);
-  if (a.fuse_size)
-    hipLaunchKernelGGL(url_copy_kernel<true>, dim3(blocks), dim3(kThreads), 0, st, a);
-  else
-    hipLaunchKernelGGL(url_copy_kernel<false>, dim3(blocks), dim3(kThreads), 0, st, a);
+  if (a.refs) {   // the refs form: nothing to copy, only the fused spans pass
+    if (a.fuse_size) hipLaunchKernelGGL((url_copy_kernel<true, true>), dim3(blocks), dim3(kThreads), 0, st, a);
+  } else if (a.fuse_size) {
+    hipLaunchKernelGGL((url_copy_kernel<true, false>), dim3(blocks), dim3(kThreads), 0, st, a);
+  } else {
+    hipLaunchKernelGGL((url_copy_kernel<false, false>), dim3(blocks), dim3(kThreads), 0, st, a);
+  }
 }
 void launch_url_plan_slow(const UrlKernelArgs& a, hipStream_t st) {
   // the list length is on the device: a workgroup per group up to the resident
