@@ -1,11 +1,13 @@
 /*
  * odigos_amd.h — C ABI of the MI355X span-processing engine.
  *
- * This is the drop-in boundary for the three gateway trace processors of the
+ * This is the drop-in boundary for the gateway trace processors of the
  * Odigos collector (reference: damemi/odigos @ 2026-02-13):
  *
  *   odigossampling       collector/processors/odigossamplingprocessor
  *   odigosurltemplate    collector/processors/odigosurltemplateprocessor
+ *   odigossqldboperationprocessor
+ *                        collector/processors/odigossqldboperationprocessor
  *   odigostrafficmetrics collector/processors/odigostrafficmetrics
  *
  * In the reference each processor is a Go processor.Factory whose
@@ -33,7 +35,7 @@
 extern "C" {
 #endif
 
-#define OSE_ABI_VERSION 4
+#define OSE_ABI_VERSION 5
 
 /* ---- error codes ---------------------------------------------------- */
 #define OSE_OK        0
@@ -117,6 +119,40 @@ extern "C" {
  * renamed span names as if TEMPLATE had run in this call (the traffic
  * processor runs after the URL processor, config_builder.go:215-229).       */
 #define OSE_STAGE_APPLY_TEMPLATE 0x20u
+/* odigossqldboperationprocessor (processor.go:30-78; the query-operation-
+ * detector profile runs it after odigosurltemplate and before
+ * odigostrafficmetrics): sql_op[i] = the operation DetectSQLOperationName
+ * (processor.go:84-115) finds in db_query, for every span whatever keep
+ * says; 0 for the spans the processor leaves alone.  A plain launch on the
+ * caller's stream: no workspace, no host wait, capturable into a hipGraph.
+ * The OTLP entry points do not carry this stage yet: ose_otlp_decode leaves
+ * db_flags / db_query / res_sql_ok NULL, and ose_otlp_encode /
+ * ose_otlp_pipeline_create return OSE_ENOTSUP for a stage mask holding
+ * either SQLOP bit.                                                         */
+#define OSE_STAGE_SQLOP        0x40u
+/* sql_op already holds an earlier call's results: SIZE counts the attribute
+ * and the longer name as if SQLOP had run in this call.  Excludes SQLOP.    */
+#define OSE_STAGE_APPLY_SQLOP  0x80u
+
+/* ---- per-span db_flags (columnarised by the shim) --------------------
+ * What odigossqldboperationprocessor/processor.go:52-61 reads from the span
+ * attribute map.                                                            */
+#define OSE_DB_HAS_QUERY   0x01u  /* Attributes().Get("db.query.text") found (:52)      */
+#define OSE_DB_HAS_OPNAME  0x02u  /* Attributes().Get("db.operation.name") found (:58),
+                                     a value of any type                              */
+
+/* ---- per-span sql_op (results): the constants of processor.go:19-28 ----
+ * OSE_SQLOP_NONE: the span is skipped or the query is "UNKNOWN".  Otherwise
+ * the shim applies PutStr("db.operation.name", NAME) (:68) and
+ * SetName(name + " " + NAME) (:71-72).                                      */
+#define OSE_SQLOP_NONE   0
+#define OSE_SQLOP_SELECT 1
+#define OSE_SQLOP_INSERT 2
+#define OSE_SQLOP_UPDATE 3
+#define OSE_SQLOP_DELETE 4
+#define OSE_SQLOP_CREATE 5
+#define OSE_SQLOP_DROP   6
+#define OSE_SQLOP_ALTER  7
 
 /* ---- grouping of spans into "traces" for odigossampling --------------
  * TRACE_ID: spans sharing a 128-bit trace_id form one trace (the contract
@@ -223,6 +259,17 @@ typedef struct ose_columns {
                               are chunk-local rule indices)                             */
   const uint8_t* attr_type;
   const uint64_t* attr_val;
+
+  /* odigossqldboperationprocessor (OSE_STAGE_SQLOP).  Per span: db_flags
+   * OSE_DB_*; db_query = AsString(db.query.text) in the arena
+   * (processor.go:64), read only where OSE_DB_HAS_QUERY is set.  Per
+   * resource: res_sql_ok 0 = shouldExcludeLanguage (processor.go:119-143) is
+   * true for the resource; NULL = every resource passes.  ose_otlp_decode
+   * does not fill them and ose_gbt_add does not carry them (the columns of
+   * ose_otlp_columns and ose_gbt_release have them NULL).                  */
+  const uint8_t* db_flags;
+  const ose_strref* db_query;
+  const uint8_t* res_sql_ok;
 } ose_columns;
 
 /* pcommon.ValueType of an attribute value in attr_type */
@@ -260,17 +307,24 @@ typedef struct ose_outputs {
    * only; the caller zeroes it and checks after synchronising):
    * 1 = in-kernel bounded spin gave up, 2 = tmpl_arena_cap too small */
   uint32_t* device_status;
+
+  /* odigossqldboperationprocessor */
+  uint8_t* sql_op;            /* [n_spans] OSE_SQLOP_* */
 } ose_outputs;
 
 typedef struct ose_engine ose_engine;
 typedef struct ose_batch ose_batch;
 
-/* Replaces the three processor.Factory.CreateTraces paths
+/* Replaces the processor.Factory.CreateTraces paths
  * (odigossamplingprocessor/factory.go:29-45 -> config.go:17-80 Validate;
  *  odigosurltemplateprocessor/factory.go:31-44 -> processor.go:27-69;
- *  odigostrafficmetrics/factory.go:34-47 -> processor.go:31-58).
+ *  odigostrafficmetrics/factory.go:34-47 -> processor.go:31-58;
+ *  odigossqldboperationprocessor/factory.go -> config.go, whose Validate
+ *  never fails).
  * cfg_json: {"odigossampling": {...}, "odigosurltemplate": {...},
- *            "odigostrafficmetrics": {...}} with the mapstructure keys of the
+ *            "odigostrafficmetrics": {...},
+ *            "odigossqldboperationprocessor": {"exclude": {"language": [...]}}}
+ * with the mapstructure keys of the
  * Go Config structs; absent sections are absent processors.  Validates
  * exactly as the Go Validate() does (same messages) and compiles every user
  * regexp to a DFA; a regexp the DFA compiler cannot express is OSE_ENOTSUP
@@ -354,8 +408,10 @@ void ose_batch_release(ose_batch* b);
 
 /* Synchronous: H2D of the batch, stages in `stage_mask`, D2H of results.
  * Replaces one ProcessTracesFunc call of each selected processor, run in
- * gateway pipeline order sample -> template -> size
- * (common/pipelinegen/config_builder.go:215-229).                           */
+ * gateway pipeline order sample -> template -> sqlop -> size
+ * (common/pipelinegen/config_builder.go:215-229).  A batch of an engine with
+ * the odigossqldboperationprocessor section also carries db_flags, db_query,
+ * res_sql_ok and sql_op.                                                    */
 int ose_process(ose_engine* eng, ose_batch* b, uint32_t stage_mask,
                 uint32_t group_mode, const ose_rand* rnd);
 

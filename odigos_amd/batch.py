@@ -23,12 +23,13 @@ COLUMN_LAYOUT = {
     "res_svc": ("res", 4), "res_svc_str": ("res", 4), "res_url_ok": ("res", 1), "res_attrset": ("res", 4),
     "res_size": ("res", 4), "scope_size": ("scope", 4), "scope_resource": ("scope", 4),
     "attr_type": ("span_key", 1), "attr_val": ("span_key", 8),
+    "db_flags": ("span", 1), "db_query": ("span", 8), "res_sql_ok": ("res", 1),
 }
 OUTPUT_LAYOUT = {
     "keep": ("span", 1), "trace_count": ("one", 4), "trace_first_span": ("span", 4), "trace_keep": ("span", 1),
     "trace_level": ("span", 1), "trace_ratio": ("span", 8), "url_out": ("span", 1), "tmpl": ("span", 8),
     "attrset_bytes": ("attrset", 8), "accepted_spans": ("one", 8), "res_bytes": ("res", 8),
-    "device_status": ("one", 16),
+    "device_status": ("one", 16), "sql_op": ("span", 1),
 }
 
 

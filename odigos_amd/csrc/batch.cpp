@@ -127,6 +127,13 @@ int Batch::build(const ose_columns& dims) {
     IN(attr_type, K * n);
     IN(attr_val, 8 * K * n);
   }
+  // odigossqldboperationprocessor's columns: only in the batches of an engine
+  // with the section (other engines' batches keep their size)
+  if (e->has_sqlop) {
+    IN(db_flags, n);
+    IN(db_query, 8 * n);
+    IN(res_sql_ok, R);
+  }
   arena_off = IN(arena, dims.arena_bytes);
   core_off = off;
   OUT(keep, n);
@@ -134,6 +141,7 @@ int Batch::build(const ose_columns& dims) {
   OUT(trace_keep, n1);
   OUT(url_out, n);
   OUT(tmpl, 8 * n);
+  if (e->has_sqlop) OUT(sql_op, n);
   core_end = off;
   const size_t o_first = OUT(trace_first_span, 4 * n1);
   const size_t o_level = OUT(trace_level, n1);

@@ -35,7 +35,11 @@ std::set<std::string> workload_set(const MatchProperties& mp) {
 }
 
 std::string ColumnizeCtx::build(const UrlTemplateConfig* url, const SamplingConfig* sampling,
-                                const TrafficMetricsConfig* traffic) {
+                                const TrafficMetricsConfig* traffic, const SqlOpConfig* sql) {
+  if (sql) {
+    sqlop = true;
+    if (sql->has_exclude) sql_exclude = sql->exclude_language;
+  }
   if (url) {
     has_exclude = url->exclude.has_value();
     has_include = url->include.has_value();
@@ -80,6 +84,18 @@ ResourceCols columnize_resource(const ColumnizeCtx& c, const AttrMap& ra) {
     const bool has_key = workload_key(ra, key);
     if (c.has_exclude && has_key && c.excl.count(key)) r.url_ok = 0;
     if (c.has_include && !(has_key && c.incl.count(key))) r.url_ok = 0;
+  }
+  // shouldExcludeLanguage (odigossqldboperationprocessor/processor.go:119-143):
+  // with a non-empty list, a resource without telemetry.sdk.language is
+  // excluded, and so is one whose AsString value is listed
+  if (c.sqlop && !c.sql_exclude.empty()) {
+    const Value* lang = ra.Get("telemetry.sdk.language");
+    if (!lang) {
+      r.sql_ok = 0;
+    } else {
+      const std::string lv = lang->AsString();
+      if (std::find(c.sql_exclude.begin(), c.sql_exclude.end(), lv) != c.sql_exclude.end()) r.sql_ok = 0;
+    }
   }
   // attributeSetFromResource (odigostrafficmetrics/processor.go:60-69)
   std::map<std::string, std::string> set;
@@ -196,6 +212,22 @@ void columnize_span(const ColumnizeCtx& c, const Span& sp, const std::vector<uin
     }
   }
   o.url_flags = f;
+  // odigossqldboperationprocessor (processor.go:52-64)
+  o.db_flags = 0;
+  o.db_query = std::string_view();
+  if (c.sqlop) {
+    const Value* q = sp.attrs.Get("db.query.text");
+    if (q) {
+      o.db_flags |= OSE_DB_HAS_QUERY;
+      if (q->type == Value::TStr) {
+        o.db_query = q->s;
+      } else {
+        o.db_query_own = q->AsString();
+        o.db_query = o.db_query_own;
+      }
+    }
+    if (sp.attrs.Get("db.operation.name")) o.db_flags |= OSE_DB_HAS_OPNAME;
+  }
 }
 
 }  // namespace ose

@@ -32,7 +32,10 @@ struct ColumnizeCtx {
   std::vector<std::string> traffic_keys;      // odigostrafficmetrics res_attributes_keys
   std::vector<SpanAttrPredicate> attr_preds;  // every span_attribute rule, level order
   AttrPlan attr_plan;                         // which ones the GPU evaluates, from which key column
-  std::string build(const UrlTemplateConfig* url, const SamplingConfig* sampling, const TrafficMetricsConfig* traffic);
+  bool sqlop = false;                         // odigossqldboperationprocessor configured
+  std::vector<std::string> sql_exclude;       // its exclude.language list
+  std::string build(const UrlTemplateConfig* url, const SamplingConfig* sampling, const TrafficMetricsConfig* traffic,
+                    const SqlOpConfig* sqlop = nullptr);
 };
 
 // per-resource columns (service ids, include/exclude, attribute set, and the
@@ -40,6 +43,7 @@ struct ColumnizeCtx {
 struct ResourceCols {
   uint32_t svc = OSE_NONE, svc_str = OSE_NONE;
   uint8_t url_ok = 1;
+  uint8_t sql_ok = 1;               // !shouldExcludeLanguage (odigossqldboperationprocessor/processor.go:119-143)
   std::vector<uint64_t> attr_res;   // span_attribute rules whose service this resource is (64 per word)
   std::vector<std::pair<std::string, std::string>> attrset;   // attribute.NewSet: sorted, last value wins
 };
@@ -61,6 +65,10 @@ struct SpanCols {
   std::vector<uint8_t> attr_type;             // per GPU key column
   std::vector<uint64_t> attr_val;             // STR values: placeholder, see attr_str
   std::vector<std::string_view> attr_str;     // STR values' bytes (per key; empty otherwise)
+  // odigossqldboperationprocessor (filled when ColumnizeCtx::sqlop)
+  uint8_t db_flags = 0;                       // OSE_DB_*
+  std::string_view db_query;                  // AsString(db.query.text)
+  std::string db_query_own;                   // its storage when the value is not a Str
 };
 void columnize_span(const ColumnizeCtx& c, const Span& sp, const std::vector<uint64_t>& attr_res, const ProtoSizer& sizer,
                     SpanCols& out);

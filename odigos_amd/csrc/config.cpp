@@ -1,4 +1,4 @@
-// config.cpp — decoding + Validate() of the three processor configs.
+// config.cpp — decoding + Validate() of the processor configs.
 // See config.hpp for the reference files restated here.
 #include "config.hpp"
 
@@ -316,6 +316,19 @@ std::string decode_traffic_config(const Json& j, TrafficMetricsConfig& out) {
   TRY(get_str_list(j, "res_attributes_keys", out.res_attributes_keys));
   TRY(get_f64(j, "sampling_ratio", out.sampling_ratio));
   if (out.sampling_ratio < 0 || out.sampling_ratio > 1) return "sampling_ratio must be between 0.0 and 1.0";
+  return "";
+}
+
+// odigossqldboperationprocessor/config.go:7-23: only decode errors
+std::string decode_sqlop_config(const Json& j, SqlOpConfig& out) {
+  out = SqlOpConfig{};
+  if (j.is_null()) return "";
+  if (!j.is_obj()) return "expected a map for odigossqldboperationprocessor config";
+  const Json* ex = j.get("exclude");
+  if (!ex || ex->is_null()) return "";
+  if (!ex->is_obj()) return "'exclude' expected a map";
+  out.has_exclude = true;
+  TRY(get_str_list(*ex, "language", out.exclude_language));
   return "";
 }
 

@@ -1,4 +1,4 @@
-// config.hpp — the three processors' Config structs, decoded from the
+// config.hpp — the processors' Config structs, decoded from the
 // mapstructure-shaped JSON the collector's confmap would hand to
 // Factory.CreateTraces, and validated with the reference's messages.
 //
@@ -6,6 +6,7 @@
 //                         internal/sampling/{error,latency,servicename,spanattribute}.go
 //   odigosurltemplate     odigosurltemplateprocessor/config.go:11-158
 //   odigostrafficmetrics  odigostrafficmetrics/config.go:9-29, factory.go:27-32
+//   odigossqldboperationprocessor  odigossqldboperationprocessor/config.go:7-23
 #pragma once
 #include <optional>
 #include <string>
@@ -69,11 +70,18 @@ struct TrafficMetricsConfig {      // config.go:9-18; default SamplingRatio 1.0 
   double sampling_ratio = 1.0;
 };
 
+// ---------------- odigossqldboperationprocessor ----------------
+struct SqlOpConfig {               // config.go:7-16; Validate never fails (:20-23)
+  bool has_exclude = false;        // Exclude != nil
+  std::vector<std::string> exclude_language;
+};
+
 // Each decode_* returns "" on success or the error the Go code would return
 // (mapstructure decode error, then Validate()).
 std::string decode_url_config(const Json& j, UrlTemplateConfig& out);
 std::string decode_sampling_config(const Json& j, SamplingConfig& out);
 std::string decode_traffic_config(const Json& j, TrafficMetricsConfig& out);
+std::string decode_sqlop_config(const Json& j, SqlOpConfig& out);
 
 // Rule-string parsing shared by Validate and the compiled tables
 // (templatize.go:97-190).

@@ -514,7 +514,7 @@ int run_stages(Engine* e, const ose_columns* c, const ose_outputs* o, uint32_t m
                const ose_rand* rnd, hipStream_t st) {
   if (!c || !o) return fail(OSE_EINVAL, "columns and outputs are required");
   if (mask & ~(OSE_STAGE_SAMPLE | OSE_STAGE_TEMPLATE | OSE_STAGE_SIZE | OSE_STAGE_APPLY_KEEP | OSE_STAGE_TEMPLATE_REFS |
-               OSE_STAGE_APPLY_TEMPLATE))
+               OSE_STAGE_APPLY_TEMPLATE | OSE_STAGE_SQLOP | OSE_STAGE_APPLY_SQLOP))
     return fail(OSE_EINVAL, "unknown stage bit");
   if ((mask & OSE_STAGE_TEMPLATE_REFS) && !(mask & OSE_STAGE_TEMPLATE))
     return fail(OSE_EINVAL, "OSE_STAGE_TEMPLATE_REFS needs OSE_STAGE_TEMPLATE");
@@ -522,6 +522,19 @@ int run_stages(Engine* e, const ose_columns* c, const ose_outputs* o, uint32_t m
     return fail(OSE_EINVAL, "OSE_STAGE_APPLY_KEEP and OSE_STAGE_SAMPLE exclude each other");
   if ((mask & OSE_STAGE_APPLY_TEMPLATE) && (mask & OSE_STAGE_TEMPLATE))
     return fail(OSE_EINVAL, "OSE_STAGE_APPLY_TEMPLATE and OSE_STAGE_TEMPLATE exclude each other");
+  if ((mask & OSE_STAGE_APPLY_SQLOP) && (mask & OSE_STAGE_SQLOP))
+    return fail(OSE_EINVAL, "OSE_STAGE_APPLY_SQLOP and OSE_STAGE_SQLOP exclude each other");
+  // odigossqldboperationprocessor: refused before anything is queued
+  if (mask & OSE_STAGE_SQLOP) {
+    if (!e->has_sqlop) return fail(OSE_EINVAL, "odigossqldboperationprocessor is not configured on this engine");
+    if (!c->db_flags || !c->db_query || !c->resource || !o->sql_op)
+      return fail(OSE_EINVAL, "SQLOP stage needs db_flags, db_query, resource and sql_op");
+  }
+  // SIZE after SQLOP (in this call or an earlier one): the spans pass is
+  // sqlop_size_span_kernel, never the one fused into url_copy_kernel
+  const bool sql_size = (mask & OSE_STAGE_SIZE) && (mask & (OSE_STAGE_SQLOP | OSE_STAGE_APPLY_SQLOP));
+  if (sql_size)
+    if (const int src = check_sqlop_size(c, o)) return src;
   // SAMPLE + TEMPLATE by trace id: the URL stage reads nothing SAMPLE writes,
   // so its launches are queued between SAMPLE's fast path and the rest of
   // SAMPLE, which is queued once the host has read the fast path's dup flag
@@ -614,7 +627,8 @@ int run_stages(Engine* e, const ose_columns* c, const ose_outputs* o, uint32_t m
   // stream is joined a second time at the end of the call
   bool early_join = false;
 #ifndef OSE_URL_JOIN_LATE
-  early_join = ust && tmpl && !rc && (mask & OSE_STAGE_TEMPLATE_REFS) && (mask & OSE_STAGE_SIZE) &&
+  // (not with sql_size: its spans pass reads the refs url_emit_slow_kernel writes)
+  early_join = ust && tmpl && !rc && (mask & OSE_STAGE_TEMPLATE_REFS) && (mask & OSE_STAGE_SIZE) && !sql_size &&
                !(OSE_DIAG && getenv("OSE_NO_FUSED_SIZE"));
 #endif
   bool join_recorded = false;
@@ -644,13 +658,16 @@ int run_stages(Engine* e, const ose_columns* c, const ose_outputs* o, uint32_t m
       if (!rc) rc = fail(OSE_EDEVICE, std::string("URL stream join: ") + hipGetErrorString(jw));
     }
   }
+  // odigossqldboperationprocessor (orderHint 150): after odigosurltemplate,
+  // before odigostrafficmetrics; it reads nothing the earlier stages write
+  if (!rc && (mask & OSE_STAGE_SQLOP)) rc = run_sqlop(e, c, o, st);
   // odigostrafficmetrics runs last, on what the earlier stages left (the
   // decisions are final here: SAMPLE's tail has been queued)
   SizeKernelArgs sa{};
   bool size_on = false;
   if (!rc && (mask & OSE_STAGE_SIZE)) rc = prepare_size(e, c, o, mask, group_mode, rnd, st, ws, size_off, sa, size_on);
   if (!rc && tmpl) {
-    if (size_on && n > 0 && !(OSE_DIAG && getenv("OSE_NO_FUSED_SIZE"))) {
+    if (size_on && n > 0 && !sql_size && !(OSE_DIAG && getenv("OSE_NO_FUSED_SIZE"))) {
       // the spans pass rides in url_copy_kernel (one walk over the spans)
       sa.kept_partials = size_partials_of(ws, size_off, c->n_scopes, c->n_resources);
       sa.n_kept_partials = url_copy_blocks(ua.n_groups);
@@ -660,7 +677,7 @@ int run_stages(Engine* e, const ose_columns* c, const ose_outputs* o, uint32_t m
     }
     rc = run_url_back(e, ua, st);
   }
-  if (!rc && size_on) rc = run_size_tail(e, sa, st);
+  if (!rc && size_on) rc = sql_size ? run_sqlop_size_tail(e, sa, o->sql_op, st) : run_size_tail(e, sa, st);
   if (ust) {
     if (join_recorded) {
       // second join: the side stream's scan and slow emit end before the
@@ -746,6 +763,11 @@ int ose_engine_create(const char* cfg_json, ose_engine** out) {
     e->has_traffic = true;
     // newThroughputMeasurementProcessor (processor.go:31-36)
     e->inverse = e->traffic.sampling_ratio != 0 ? (int64_t)(1.0 / e->traffic.sampling_ratio) : 0;
+  }
+  if (const Json* j = root.get("odigossqldboperationprocessor")) {
+    err = decode_sqlop_config(*j, e->sqlop);
+    if (!err.empty()) { delete e; return fail(OSE_EINVAL, err); }
+    e->has_sqlop = true;
   }
   if (e->has_url) {
     int rc = build_url_blob(e->url, e->url_blob_host, e->max_name);
@@ -899,7 +921,7 @@ int ose_engine_get_info(const ose_engine* eng, ose_engine_info* info) {
   if (!eng || !info) return fail(OSE_EINVAL, "NULL argument");
   const Engine* e = reinterpret_cast<const Engine*>(eng);
   info->stages = (e->has_sampling ? OSE_STAGE_SAMPLE : 0) | (e->has_url ? OSE_STAGE_TEMPLATE : 0) |
-                 (e->has_traffic ? OSE_STAGE_SIZE : 0);
+                 (e->has_traffic ? OSE_STAGE_SIZE : 0) | (e->has_sqlop ? OSE_STAGE_SQLOP : 0);
   info->max_template_name = e->max_name;
   info->inverse_sampling = e->inverse;
   info->traffic_sampling_ratio = e->traffic.sampling_ratio;

@@ -115,7 +115,8 @@ struct Engine {
   UrlTemplateConfig url;
   SamplingConfig sampling;
   TrafficMetricsConfig traffic;
-  bool has_url = false, has_sampling = false, has_traffic = false;
+  SqlOpConfig sqlop;
+  bool has_url = false, has_sampling = false, has_traffic = false, has_sqlop = false;
   // ose_engine_set_option: alternative implementations of the OTLP legs
   // (the default path is the fast one; these select the others, for tests
   // that compare the two)
@@ -226,6 +227,12 @@ int prepare_size(Engine* e, const ose_columns* c, const ose_outputs* o, uint32_t
 uint32_t* size_partials_of(Workspace* ws, size_t off, uint64_t n_scopes, uint64_t n_resources);
 int run_size_tail(Engine* e, const SizeKernelArgs& a, hipStream_t st);
 size_t size_scratch_bytes(uint64_t n_scopes, uint64_t n_resources);
+// odigossqldboperationprocessor (sqlop_host.cpp): the SQLOP launch, the
+// columns SIZE needs after it, and run_size_tail with the spans pass that
+// counts what sql_op adds
+int run_sqlop(Engine* e, const ose_columns* c, const ose_outputs* o, hipStream_t st);
+int check_sqlop_size(const ose_columns* c, const ose_outputs* o);
+int run_sqlop_size_tail(Engine* e, const SizeKernelArgs& a, const uint8_t* sql_op, hipStream_t st);
 // every rule chunk's endpoint bits of the spans as planes of n words (a
 // config with spilled route bytes: Engine::sampling_spill), sampling_host.cpp
 int spill_endpoint_planes(Engine* e, const ose_columns* c, Workspace* ws, hipStream_t st, const uint64_t** out);

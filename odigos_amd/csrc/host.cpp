@@ -58,6 +58,10 @@ void HostBatch::bind() {
   cols.attr_match_words = attr_words;
   cols.attr_type = cols.n_attr_keys ? attr_type.data() : nullptr;
   cols.attr_val = cols.n_attr_keys ? attr_val.data() : nullptr;
+  cols.db_flags = has_sqlop ? db_flags.data() : nullptr;
+  cols.db_query = has_sqlop ? db_query.data() : nullptr;
+  cols.res_sql_ok = has_sqlop ? res_sql_ok.data() : nullptr;
+  outs.sql_op = has_sqlop ? sql_op.data() : nullptr;
   outs.keep = keep.data();
   outs.trace_count = trace_count.data();
   outs.trace_first_span = trace_first_span.data();
@@ -77,7 +81,10 @@ void HostBatch::bind() {
 
 namespace {
 
-const char* kProcType[] = {"odigossampling", "odigosurltemplate", "odigostrafficmetrics", "pipeline"};
+const char* kProcType[] = {"odigossampling", "odigosurltemplate", "odigostrafficmetrics", "pipeline",
+                           "odigossqldboperationprocessor"};
+// processor.go:19-27, indexed by OSE_SQLOP_*
+const char* kSqlOpName[] = {"", "SELECT", "INSERT", "UPDATE", "DELETE", "CREATE", "DROP", "ALTER"};
 
 }  // namespace
 
@@ -91,13 +98,16 @@ TracesProcessor::TracesProcessor(ProcKind k, const Json& cfg) : kind_(k), cfg_js
       if (const Json* j = c.get("odigossampling")) { err_ = decode_sampling_config(*j, sampling_); has_sampling_ = true; }
       if (err_.empty()) if (const Json* j = c.get("odigosurltemplate")) { err_ = decode_url_config(*j, url_); has_url_ = true; }
       if (err_.empty()) if (const Json* j = c.get("odigostrafficmetrics")) { err_ = decode_traffic_config(*j, traffic_); has_traffic_ = true; }
+      if (err_.empty()) if (const Json* j = c.get("odigossqldboperationprocessor")) { err_ = decode_sqlop_config(*j, sqlop_); has_sqlop_ = true; }
       group_mode = OSE_GROUP_TRACE_ID;
       break;
+    case ProcKind::SqlOp: err_ = decode_sqlop_config(c, sqlop_); has_sqlop_ = true; break;
   }
   // span_attribute conditions: compiled here (json ones run in the walk);
   // newUrlTemplateProcessor's errors are decode_url_config's (factory.go:37-40)
   if (err_.empty())
-    err_ = ctx_.build(has_url_ ? &url_ : nullptr, has_sampling_ ? &sampling_ : nullptr, has_traffic_ ? &traffic_ : nullptr);
+    err_ = ctx_.build(has_url_ ? &url_ : nullptr, has_sampling_ ? &sampling_ : nullptr, has_traffic_ ? &traffic_ : nullptr,
+                      has_sqlop_ ? &sqlop_ : nullptr);
 }
 
 TracesProcessor::~TracesProcessor() {
@@ -105,7 +115,8 @@ TracesProcessor::~TracesProcessor() {
 }
 
 uint32_t TracesProcessor::stages() const {
-  return (has_sampling_ ? OSE_STAGE_SAMPLE : 0) | (has_url_ ? OSE_STAGE_TEMPLATE : 0) | (has_traffic_ ? OSE_STAGE_SIZE : 0);
+  return (has_sampling_ ? OSE_STAGE_SAMPLE : 0) | (has_url_ ? OSE_STAGE_TEMPLATE : 0) | (has_traffic_ ? OSE_STAGE_SIZE : 0) |
+         (has_sqlop_ ? OSE_STAGE_SQLOP : 0);
 }
 
 int TracesProcessor::ensure_engine() {   // callers hold mu_
@@ -170,6 +181,12 @@ std::unique_ptr<HostBatch> TracesProcessor::Columnarize(const Traces& td, bool k
   hb->res_svc.resize(R);
   hb->res_svc_str.resize(R);
   hb->res_url_ok.resize(R);
+  hb->has_sqlop = ctx_.sqlop;
+  if (ctx_.sqlop) {
+    hb->db_flags.resize(N);
+    hb->db_query.resize(N);
+    hb->res_sql_ok.resize(R);
+  }
   hb->res_attrset.resize(R);
   hb->res_size.resize(R);
   hb->scope_size.resize(S);
@@ -206,6 +223,7 @@ std::unique_ptr<HostBatch> TracesProcessor::Columnarize(const Traces& td, bool k
       hb->res_svc[ri] = rc.svc;
       hb->res_svc_str[ri] = rc.svc_str;
       hb->res_url_ok[ri] = rc.url_ok;
+      if (ctx_.sqlop) hb->res_sql_ok[ri] = rc.sql_ok;
       auto it = g.ids.find(rc.attrset);
       if (it == g.ids.end()) {
         it = g.ids.emplace(rc.attrset, (uint32_t)g.sets.size()).first;
@@ -244,6 +262,10 @@ std::unique_ptr<HostBatch> TracesProcessor::Columnarize(const Traces& td, bool k
           hb->route[i] = sc.has_route ? add_str(sc.route) : ose_strref{~0u, 0};
           hb->url_flags[i] = sc.url_flags;
           hb->path[i] = (sc.url_flags & OSE_URL_PATH_MASK) != OSE_URL_PATH_NONE ? add_str(sc.path) : ose_strref{~0u, 0};
+          if (ctx_.sqlop) {
+            hb->db_flags[i] = sc.db_flags;
+            hb->db_query[i] = (sc.db_flags & OSE_DB_HAS_QUERY) ? add_str(sc.db_query) : ose_strref{~0u, 0};
+          }
           i++;
         }
         sidx++;
@@ -279,6 +301,10 @@ std::unique_ptr<HostBatch> TracesProcessor::Columnarize(const Traces& td, bool k
       rt = rt.off == ~0u ? ose_strref{0, 0} : ose_strref{rt.off + base, rt.len};
       ose_strref& pt = hb->path[i];
       pt = pt.off == ~0u ? ose_strref{0, 0} : ose_strref{pt.off + base, pt.len};
+      if (ctx_.sqlop) {
+        ose_strref& qt = hb->db_query[i];
+        qt = qt.off == ~0u ? ose_strref{0, 0} : ose_strref{qt.off + base, qt.len};
+      }
       if (base)
         for (size_t q = 0; q < nk; q++)
           if (hb->attr_type[q * N + i] == OSE_ATTR_STR) hb->attr_val[q * N + i] += base;   // off in the low half
@@ -305,6 +331,12 @@ std::unique_ptr<HostBatch> TracesProcessor::Columnarize(const Traces& td, bool k
   hb->trace_count.assign(1, 0);
   hb->url_out.assign(nn, 0);
   hb->tmpl.assign(nn, ose_strref{0, 0});
+  if (ctx_.sqlop) {
+    hb->sql_op.assign(nn, 0);
+    if (hb->db_flags.empty()) hb->db_flags.push_back(0);
+    if (hb->db_query.empty()) hb->db_query.push_back(ose_strref{0, 0});
+    if (hb->res_sql_ok.empty()) hb->res_sql_ok.push_back(0);
+  }
   // capacity bound: every output byte comes from a path byte, a separator or
   // a name (the test seam's oracle writes here; ProcessTraces sizes it to
   // what the device used when it reads the outputs back)
@@ -421,6 +453,20 @@ void TracesProcessor::Apply(HostBatch& hb, Traces& td) {
               std::swap(sp.name, nm);
               old.strs.push_back(std::move(nm));
             }
+          }
+          // odigossqldboperationprocessor, after the URL mutation (orderHint 150):
+          // PutStr (processor.go:68; the key is absent, so it is appended) and
+          // SetName(name + " " + op) (:71-72)
+          if (kept && (st & OSE_STAGE_SQLOP) && o.sql_op[i] && o.sql_op[i] <= OSE_SQLOP_ALTER) {
+            const char* opn = kSqlOpName[o.sql_op[i]];
+            put_str(old, sp.attrs, "db.operation.name", opn);
+            std::string nm;
+            nm.reserve(sp.name.size() + 1 + 6);
+            nm = sp.name;
+            nm += ' ';
+            nm += opn;
+            std::swap(sp.name, nm);
+            old.strs.push_back(std::move(nm));
           }
           if (by_trace && kept) {   // RemoveIf, keeping order
             if (w != q) std::swap(ss.spans[w], sp);
@@ -547,6 +593,11 @@ int TracesProcessor::ProcessTraces(Traces& td, double* phase_s) {
     cp(c->attr_type, hb->cols.attr_type, (size_t)hb->cols.n_attr_keys * n);
     cp(c->attr_val, hb->cols.attr_val, 8 * (size_t)hb->cols.n_attr_keys * n);
   }
+  if (has_sqlop_) {
+    cp(c->db_flags, hb->cols.db_flags, n);
+    cp(c->db_query, hb->cols.db_query, 8 * n);
+    cp(c->res_sql_ok, hb->cols.res_sql_ok, R);
+  }
   std::memset(o->attrset_bytes, 0, 8 * (size_t)A);
   std::memset(o->accepted_spans, 0, 8);
   lap(1);
@@ -561,6 +612,7 @@ int TracesProcessor::ProcessTraces(Traces& td, double* phase_s) {
   }
   cp(hb->outs.url_out, o->url_out, n);
   cp(hb->outs.tmpl, o->tmpl, 8 * n);
+  if (has_sqlop_) cp(hb->outs.sql_op, o->sql_op, n);
   uint64_t used = *o->tmpl_arena_used;
   if (used + 16 > hb->tmpl_arena.size()) { hb->tmpl_arena.resize(used + 16); hb->bind(); }
   cp(hb->outs.tmpl_arena, o->tmpl_arena, used);
@@ -616,7 +668,8 @@ extern "C" {
 const char* osehost_last_error(void) { return g_host_err.c_str(); }
 
 // Factory.CreateTraces for "odigossampling" | "odigosurltemplate" |
-// "odigostrafficmetrics" | "pipeline" (all three, gateway order).  NULL on a
+// "odigostrafficmetrics" | "odigossqldboperationprocessor" | "pipeline" (the
+// configured sections, gateway order).  NULL on a
 // config error (message in osehost_last_error).
 void* osehost_processor_create(const char* type, const char* cfg_json) {
   ProcKind k;
@@ -625,6 +678,7 @@ void* osehost_processor_create(const char* type, const char* cfg_json) {
   else if (t == "odigosurltemplate") k = ProcKind::UrlTemplate;
   else if (t == "odigostrafficmetrics") k = ProcKind::TrafficMetrics;
   else if (t == "pipeline") k = ProcKind::Pipeline;
+  else if (t == "odigossqldboperationprocessor") k = ProcKind::SqlOp;
   else { g_host_err = "unknown processor type: " + t; return nullptr; }
   Json cfg;
   try {

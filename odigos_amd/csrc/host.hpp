@@ -1,9 +1,10 @@
-// host.hpp — C++ mirror of the three processors' Go operator interface
+// host.hpp — C++ mirror of the processors' Go operator interface
 // (processor.Factory -> CreateTraces -> ProcessTracesFunc) above the C ABI.
 //
 //   NewFactory()                     odigossamplingprocessor/factory.go:13-19,
 //                                    odigosurltemplateprocessor/factory.go:19-25,
-//                                    odigostrafficmetrics/factory.go:18-26
+//                                    odigostrafficmetrics/factory.go:18-26,
+//                                    odigossqldboperationprocessor/factory.go
 //   Factory::CreateDefaultConfig()   sampling factory.go:21-27 (empty rule lists),
 //                                    urltemplate factory.go:27-29 (&Config{}),
 //                                    trafficmetrics factory.go:28-32 (SamplingRatio 1.0)
@@ -40,6 +41,10 @@ struct HostBatch {
   std::vector<uint8_t> res_url_ok;
   std::vector<uint8_t> attr_type;           // key-major [n_attr_keys * n]
   std::vector<uint64_t> attr_val;
+  // odigossqldboperationprocessor: bound when has_sqlop (NULL otherwise)
+  bool has_sqlop = false;
+  std::vector<uint8_t> db_flags, res_sql_ok, sql_op;
+  std::vector<ose_strref> db_query;
   // outputs
   std::vector<uint8_t> keep, trace_keep, trace_level, url_out, tmpl_arena;
   std::vector<uint32_t> trace_count, trace_first_span, device_status;
@@ -51,7 +56,7 @@ struct HostBatch {
   void bind();   // point cols/outs at the vectors
 };
 
-enum class ProcKind { Sampling, UrlTemplate, TrafficMetrics, Pipeline };
+enum class ProcKind { Sampling, UrlTemplate, TrafficMetrics, Pipeline, SqlOp };
 
 struct Counter {   // one otel Int64Counter data point
   std::vector<std::pair<std::string, std::string>> attrs;
@@ -85,7 +90,8 @@ class TracesProcessor {
   UrlTemplateConfig url_;
   SamplingConfig sampling_;
   TrafficMetricsConfig traffic_;
-  bool has_url_ = false, has_sampling_ = false, has_traffic_ = false;
+  SqlOpConfig sqlop_;
+  bool has_url_ = false, has_sampling_ = false, has_traffic_ = false, has_sqlop_ = false;
   ColumnizeCtx ctx_;   // the walk's view of the config (columnize.hpp)
   ose_engine* eng_ = nullptr;
   uint64_t seed_ = 0x0D16A5EEDull;

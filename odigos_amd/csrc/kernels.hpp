@@ -476,6 +476,28 @@ void launch_size_spans(const SizeKernelArgs& a, hipStream_t st);
 void launch_size_tail(const SizeKernelArgs& a, hipStream_t st);
 void launch_size_fix(const SizeKernelArgs& a, hipStream_t st);
 
+// odigossqldboperationprocessor (sqlop_kernel.hip): one lane per span,
+// sql_op[i] = OSE_SQLOP_* of db_query[i] where db_flags[i] is HAS_QUERY
+// without HAS_OPNAME and the span's resource passes res_sql_ok, else 0.
+struct SqlOpArgs {
+  uint64_t n_spans;
+  const uint8_t* arena;
+  const uint8_t* db_flags;
+  const ose_strref* db_query;
+  const uint32_t* resource;
+  const uint8_t* res_sql_ok;   // may be null (no exclude list)
+  uint8_t* sql_op;
+};
+void launch_sqlop(const SqlOpArgs& a, hipStream_t st);
+// The spans pass of the size stage after SQLOP / APPLY_SQLOP: size_span_kernel
+// plus the KeyValue and the longer name of the spans with sql_op != 0.
+// sz.name_len is read whether or not sz.templated is set.
+struct SqlSizeArgs {
+  SizeKernelArgs sz;
+  const uint8_t* sql_op;
+};
+void launch_sqlop_size_spans(const SqlSizeArgs& a, hipStream_t st);
+
 // span_attribute conditions (attr_kernel.hip): out[i] = host_bits[i] &
 // host_mask | the bits of the GPU-evaluated rules the span meets.
 struct AttrArgs {

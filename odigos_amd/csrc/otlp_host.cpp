@@ -1905,6 +1905,9 @@ int encode_threads() { return parallel_width(); }
 int ose_otlp_encode(ose_engine* eng, const ose_otlp_batch* bb, const ose_outputs* outs, uint32_t stages,
                     uint32_t group_mode, const ose_router* router, void* hip_stream, ose_otlp_out** out) {
   if (!eng || !bb || !out) return fail(OSE_EINVAL, "NULL argument");
+  // odigossqldboperationprocessor's attribute and name are not re-encoded yet
+  if (stages & (OSE_STAGE_SQLOP | OSE_STAGE_APPLY_SQLOP))
+    return fail(OSE_ENOTSUP, "ose_otlp_encode does not write odigossqldboperationprocessor's attribute and span name");
   Engine* e = reinterpret_cast<Engine*>(eng);
   auto* b = const_cast<OtlpBatchImpl*>(reinterpret_cast<const OtlpBatchImpl*>(bb));
   if (b->e != e) return fail(OSE_EINVAL, "the batch belongs to another engine");

@@ -486,6 +486,9 @@ int ose_otlp_pipeline_create(ose_engine* eng, const ose_router* router, uint32_t
                              ose_otlp_pipeline** out) {
   if (!eng || !out) return fail(OSE_EINVAL, "NULL argument");
   *out = nullptr;
+  if (stages & (OSE_STAGE_SQLOP | OSE_STAGE_APPLY_SQLOP))
+    return fail(OSE_ENOTSUP, "the OTLP path does not carry odigossqldboperationprocessor (db.query.text is not decoded, "
+                             "the attribute and name are not re-encoded)");
   if (stages & ~(OSE_STAGE_SAMPLE | OSE_STAGE_TEMPLATE | OSE_STAGE_SIZE))
     return fail(OSE_EINVAL, "the pipeline runs SAMPLE, TEMPLATE and SIZE only");
   Engine* e = reinterpret_cast<Engine*>(eng);

@@ -2,7 +2,8 @@
 
 ``Processor(type, cfg)`` mirrors ``NewFactory().CreateTraces(...)`` of the
 reference's ``odigossampling`` / ``odigosurltemplate`` /
-``odigostrafficmetrics`` (plus ``pipeline``: all three in gateway order), and
+``odigostrafficmetrics`` / ``odigossqldboperationprocessor`` (plus ``pipeline``:
+the configured ones in gateway order), and
 ``consume`` mirrors ``ProcessTracesFunc`` on OTLP/JSON traces.
 """
 from __future__ import annotations
@@ -13,7 +14,8 @@ from typing import Any
 
 from . import native
 
-PROCESSOR_TYPES = ("odigossampling", "odigosurltemplate", "odigostrafficmetrics", "pipeline")
+PROCESSOR_TYPES = ("odigossampling", "odigosurltemplate", "odigostrafficmetrics", "pipeline",
+                   "odigossqldboperationprocessor")
 
 
 def _enc_str(s) -> str:

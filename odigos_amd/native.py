@@ -36,6 +36,12 @@ URL_PATH_NONE = 0x00
 URL_PATH_RAW = 0x10
 URL_PATH_TARGET = 0x20
 
+# db_flags / sql_op (odigossqldboperationprocessor)
+DB_HAS_QUERY = 0x01
+DB_HAS_OPNAME = 0x02
+SQLOP_NONE, SQLOP_SELECT, SQLOP_INSERT, SQLOP_UPDATE, SQLOP_DELETE, SQLOP_CREATE, SQLOP_DROP, SQLOP_ALTER = range(8)
+SQLOP_NAMES = ("UNKNOWN", "SELECT", "INSERT", "UPDATE", "DELETE", "CREATE", "DROP", "ALTER")
+
 OUT_SET_ATTR = 0x01
 OUT_RENAME = 0x02
 
@@ -45,6 +51,8 @@ STAGE_SIZE = 0x4
 STAGE_APPLY_KEEP = 0x8
 STAGE_TEMPLATE_REFS = 0x10
 STAGE_APPLY_TEMPLATE = 0x20
+STAGE_SQLOP = 0x40
+STAGE_APPLY_SQLOP = 0x80
 XREC_BYTES = 56
 
 GROUP_TRACE_ID = 0
@@ -76,7 +84,8 @@ class Columns(C.Structure):
         ("n_spans", C.c_uint64), ("n_resources", C.c_uint32), ("n_scopes", C.c_uint32),
         ("n_attrsets", C.c_uint32), ("attr_match_words", C.c_uint32), ("arena_bytes", C.c_uint64),
     ] + [(f, _p) for f in COLUMN_FIELDS] + [("svc_match", _p), ("n_attr_keys", C.c_uint32), ("match_planes", C.c_uint32),
-                                            ("attr_type", _p), ("attr_val", _p)]
+                                            ("attr_type", _p), ("attr_val", _p),
+                                            ("db_flags", _p), ("db_query", _p), ("res_sql_ok", _p)]
 
 
 class Outputs(C.Structure):
@@ -87,6 +96,7 @@ class Outputs(C.Structure):
         ("tmpl_arena_used", _p),
         ("attrset_bytes", _p), ("accepted_spans", _p), ("res_bytes", _p),
         ("device_status", _p),
+        ("sql_op", _p),
     ]
 
 
@@ -222,6 +232,7 @@ def lib() -> C.CDLL:
         "osehost_regex_match_host": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint64,
                                                C.POINTER(C.c_int)]),
         "osehost_span_attr_eval": (C.c_int, [C.c_char_p, C.c_char_p]),
+        "osehost_sqlop_detect": (C.c_uint32, [C.c_char_p, C.c_size_t]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
