@@ -125,10 +125,13 @@ extern "C" {
  * (processor.go:84-115) finds in db_query, for every span whatever keep
  * says; 0 for the spans the processor leaves alone.  A plain launch on the
  * caller's stream: no workspace, no host wait, capturable into a hipGraph.
- * The OTLP entry points do not carry this stage yet: ose_otlp_decode leaves
- * db_flags / db_query / res_sql_ok NULL, and ose_otlp_encode /
- * ose_otlp_pipeline_create return OSE_ENOTSUP for a stage mask holding
- * either SQLOP bit.                                                         */
+ * The OTLP entry points carry this stage under the engine option
+ * "otlp_sqlop" (ose_engine_set_option): ose_otlp_decode then fills db_flags /
+ * db_query / res_sql_ok from the message, ose_otlp_encode writes the
+ * attribute and the name, ose_otlp_pipeline_create accepts OSE_STAGE_SQLOP.
+ * The option is off by default in this ABI version (the columns stay NULL and
+ * the two calls return OSE_ENOTSUP for a stage mask holding either SQLOP
+ * bit, as before); the default flips to on at the next ABI version.         */
 #define OSE_STAGE_SQLOP        0x40u
 /* sql_op already holds an earlier call's results: SIZE counts the attribute
  * and the longer name as if SQLOP had run in this call.  Excludes SQLOP.    */
@@ -265,8 +268,10 @@ typedef struct ose_columns {
    * (processor.go:64), read only where OSE_DB_HAS_QUERY is set.  Per
    * resource: res_sql_ok 0 = shouldExcludeLanguage (processor.go:119-143) is
    * true for the resource; NULL = every resource passes.  ose_otlp_decode
-   * does not fill them and ose_gbt_add does not carry them (the columns of
-   * ose_otlp_columns and ose_gbt_release have them NULL).                  */
+   * fills them under the engine option "otlp_sqlop" only (db_query then
+   * points into the message bytes, or at the host pass's AsString text after
+   * them; else the columns of ose_otlp_columns are NULL); ose_gbt_add does not
+   * carry them (the columns of ose_gbt_release have them NULL).             */
   const uint8_t* db_flags;
   const ose_strref* db_query;
   const uint8_t* res_sql_ok;
@@ -394,6 +399,16 @@ int ose_engine_attr_key(const ose_engine* eng, uint32_t k, const char** key, uin
  *   "otlp_host_resources"  ResourceSpans on the host, ScopeSpans on the GPU
  *   "otlp_host_scopes"     ResourceSpans and ScopeSpans on the host
  *   "encode_host"          ose_otlp_encode always uses the host encoder
+ * and one feature switch:
+ *   "otlp_sqlop"           the OTLP path carries odigossqldboperationprocessor:
+ *                          ose_otlp_decode fills db_flags / db_query /
+ *                          res_sql_ok, ose_otlp_encode applies sql_op, and
+ *                          ose_otlp_pipeline_create accepts OSE_STAGE_SQLOP.
+ *                          It applies to decodes, and to encodes and pipelines
+ *                          created, after it is set.  OSE_EINVAL on an engine
+ *                          without the odigossqldboperationprocessor section.
+ *                          Off by default; on by default from the next ABI
+ *                          version.
  * OSE_EINVAL for any other name.                                            */
 int ose_engine_set_option(ose_engine* eng, const char* name, int64_t value);
 
@@ -551,7 +566,11 @@ int ose_allreduce_counters(const int64_t* local, int64_t* node, uint64_t n, void
  * that needs AsString or net/url.Parse, nested values, json span_attribute
  * keys, unusual ids or fields) get a host pass; ose_otlp_host_spans says how
  * many.  Strings are referenced in place: the arena is the message bytes,
- * followed by the host pass's strings.  What UnmarshalTraces rejects is
+ * followed by the host pass's strings.  Under the engine option
+ * "otlp_sqlop" a second GPU pass reads db.query.text / db.operation.name of
+ * every span (db_flags, db_query; a query value that is not a string takes
+ * the host pass for AsString) and res_sql_ok comes with the resource columns
+ * (telemetry.sdk.language).  What UnmarshalTraces rejects is
  * OSE_EINVAL.  Asynchronous work is on hip_stream; the call returns when
  * the columns are complete on that stream.  res_attrset ids index the
  * attribute sets ose_otlp_attrset returns ({"key": "value", ...}).         */
@@ -594,7 +613,15 @@ const char* ose_router_pipeline(const ose_router* r, uint32_t k);   /* owned by 
  * ose_process_device wrote for this batch with `stages` / `group_mode`
  * (device or host memory; read on hip_stream): keep (or trace_keep[0] with
  * OSE_GROUP_BATCH) removes spans, emptied scopes and resources, url_out /
- * tmpl rename and template the kept spans.  With a router the outputs are
+ * tmpl rename and template the kept spans.  Under the engine option
+ * "otlp_sqlop", OSE_STAGE_SQLOP or OSE_STAGE_APPLY_SQLOP in `stages` (both
+ * mean: apply outs->sql_op; both together, or a NULL sql_op, are OSE_EINVAL)
+ * writes what odigossqldboperationprocessor/processor.go:68-72 does to the
+ * span odigosurltemplate has edited: PutStr("db.operation.name", NAME)
+ * (the first KeyValue with the key replaced where it stands, else a new one
+ * after the last attribute, after an appended http.route / url.template) and
+ * SetName(name + " " + NAME).  Without the option either bit is
+ * OSE_ENOTSUP.  With a router the outputs are
  * its pipelines then "default" (ose_router_pipelines + 1 of them); without,
  * one output.  Each output is a serialized TracesData, byte for byte what
  * pdata's marshaler writes for the processed traces; n_resources == 0 means
@@ -623,7 +650,11 @@ void ose_otlp_out_release(ose_otlp_out* o);
  * its requests, and read (and reset) with ose_otlp_pipeline_counters:
  * {"accepted_spans": n, "data_size": [[{attributes}, bytes], ...], plus the
  * batching statistics}.  max_batch_bytes bounds a batch's message bytes (0:
- * 64 MiB; a larger request runs alone).  The router (may be NULL) must
+ * 64 MiB; a larger request runs alone).  `stages` holds SAMPLE, TEMPLATE,
+ * SIZE and, on an engine whose option "otlp_sqlop" is on when the pipeline is
+ * created, SQLOP (sample -> template -> sqlop -> size; the data_size counters
+ * include what the stage adds); any other bit is OSE_EINVAL, either SQLOP bit
+ * without the option OSE_ENOTSUP.  The router (may be NULL) must
  * outlive the pipeline; the pipeline holds a reference on the engine.     */
 typedef struct ose_otlp_pipeline ose_otlp_pipeline;
 int ose_otlp_pipeline_create(ose_engine* eng, const ose_router* router, uint32_t stages, uint64_t max_batch_bytes,

@@ -71,6 +71,8 @@ class Generator:
             L.osegen_free.argtypes = [C.c_void_p]
             L.osegen_otlp.restype = C.c_void_p
             L.osegen_otlp.argtypes = [C.POINTER(native.Columns), C.c_int, C.POINTER(C.c_uint64)]
+            L.osegen_otlp_sql.restype = C.c_void_p
+            L.osegen_otlp_sql.argtypes = [C.POINTER(native.Columns), C.c_int, C.POINTER(C.c_uint64), C.c_uint32]
             L.osegen_otlp_free.argtypes = [C.c_void_p]
             Generator._L = L
         if world is None:
@@ -90,10 +92,11 @@ class Generator:
             n = (n + 15) // 16 * 16 + 16
         return host_array(getattr(self.cols, field), n)
 
-    def otlp(self, threads: int = 8) -> bytes:
-        """The batch as a serialized OTLP TracesData (gen_otlp.cpp)."""
+    def otlp(self, threads: int = 8, sql_every: int = 0) -> bytes:
+        """The batch as a serialized OTLP TracesData (gen_otlp.cpp); sql_every:
+        one span in that many also carries a db.query.text (0: none)."""
         n = C.c_uint64()
-        p = Generator._L.osegen_otlp(C.byref(self.cols), threads, C.byref(n))
+        p = Generator._L.osegen_otlp_sql(C.byref(self.cols), threads, C.byref(n), sql_every)
         try:   # (string_at takes an int size: messages above 2 GiB need the array view)
             return C.cast(p, C.POINTER(C.c_char * n.value)).contents.raw
         finally:

@@ -2,12 +2,13 @@
 // routing (odigosrouterconnector, collector/connectors/odigosrouterconnector/
 // connector.go:147-237, routingmap.go:34-103) and the exporters' marshal step
 // (ptrace.ProtoMarshaler.MarshalTraces) applied to a batch the decoder left in
-// HBM, with the stages' decisions (keep, url_out, template refs) beside it.
+// HBM, with the stages' decisions (keep, url_out, template refs, sql_op) beside it.
 // It is the device form of otlp_encode.cpp's two passes and writes the same
 // bytes:
 //   sizing   enc_span_kernel (a lane per span: its framed size, and for a
-//            renamed / templated span the edit plan — where the name field
-//            and the target KeyValue go), enc_scope_kernel (a lane per
+//            renamed / templated span or one with a sql_op the edit plan —
+//            where the name field, the target KeyValue and the
+//            db.operation.name KeyValue go), enc_scope_kernel (a lane per
 //            scope), enc_res_kernel (a lane per resource: header, schema,
 //            record size, and its pipelines from the Resource's k8s
 //            attributes);
@@ -49,6 +50,15 @@ __device__ __forceinline__ uint64_t kv_len(bool client, uint64_t tl) {
   return field_len(client ? 12 : 10) + field_len(field_len(tl));
 }
 
+// odigossqldboperationprocessor's KeyValue{"db.operation.name", AnyValue{NAME}} body size
+// and strlen(NAME) (processor.go:19-27; otlp_encode.cpp sql_kv_len / sql_op_len)
+__device__ __forceinline__ uint32_t sql_op_len(uint32_t op) { return op == OSE_SQLOP_DROP ? 4u : op == OSE_SQLOP_ALTER ? 5u : 6u; }
+__device__ __forceinline__ uint64_t sql_kv_len(uint32_t op) { return field_len(17) + field_len(field_len(sql_op_len(op))); }
+__device__ const char* sql_op_name(uint32_t op) {
+  return op == OSE_SQLOP_SELECT ? "SELECT" : op == OSE_SQLOP_INSERT ? "INSERT" : op == OSE_SQLOP_UPDATE ? "UPDATE"
+       : op == OSE_SQLOP_DELETE ? "DELETE" : op == OSE_SQLOP_CREATE ? "CREATE" : op == OSE_SQLOP_DROP ? "DROP" : "ALTER";
+}
+
 __device__ __forceinline__ void flag(const EncArgs& a, uint32_t f) { atomicOr(a.flags, f); }
 }  // namespace
 
@@ -56,7 +66,10 @@ __device__ __forceinline__ void flag(const EncArgs& a, uint32_t f) { atomicOr(a.
 // Enc::rewrite / plan_edit (otlp_encode.cpp) for the spans whose encoding is
 // pdata's; a span that is not (span_size != its length) is re-marshaled by
 // the host encoder, so it flags the call.
-__global__ __launch_bounds__(kERec) void enc_span_kernel(EncArgs a) {
+// kSql: the call applies sql_op (enc_span_sql_kernel); without, op is a
+// constant 0 and the code is what it was before the stage existed
+template <bool kSql>
+__device__ __forceinline__ void enc_span_body(const EncArgs& a) {
   const uint64_t stride = (uint64_t)gridDim.x * kERec;
   uint32_t fb = 0;
   for (uint64_t i = (uint64_t)blockIdx.x * kERec + threadIdx.x; i < a.n_spans; i += stride) {
@@ -67,24 +80,28 @@ __global__ __launch_bounds__(kERec) void enc_span_kernel(EncArgs a) {
     const uint64_t ref = a.span_ref[i];
     const uint32_t off = (uint32_t)ref, L = (uint32_t)(ref >> 32);
     const uint32_t u = a.url_out ? a.url_out[i] : 0u;
+    const uint32_t op = kSql ? (uint32_t)a.sql_op[i] : 0u;
     const bool canonical = a.span_size[i] == L;
     a.span_out[i] = (uint32_t)field_len(L);
-    if (!canonical) {   // Enc::remarshal
+    if (!canonical || op > OSE_SQLOP_ALTER) {   // Enc::remarshal; a sql_op the host reports
       fb |= kEncFbSpan;
       continue;
     }
-    if (!u) continue;   // verbatim
-    const ose_strref t = a.tmpl[i];
-    if ((uint64_t)t.off + t.len > *a.tmpl_used) {
+    if (!u && !op) continue;   // verbatim
+    const ose_strref t = u ? a.tmpl[i] : ose_strref{0, 0};
+    if (u && (uint64_t)t.off + t.len > *a.tmpl_used) {
       fb |= kEncFbTmpl;
       continue;
     }
     // plan_edit: fields ascend, so the new name takes field 5's place (or
     // goes before the first later field) and the target KeyValue replaces
     // the first one with its key or goes after the last attribute
-    uint32_t name_a = L, name_b = L, attr_a = L, attr_b = L;
+    // With op the name also gets " " + NAME (after the URL stage's name, or
+    // the span's own) and db.operation.name is put the same way, after an
+    // appended target KeyValue.
+    uint32_t name_a = L, name_b = L, attr_a = L, attr_b = L, sql_a = L, sql_b = L, own_off = 0, own_len = 0;
     int32_t kind = 0;
-    bool name_set = false, attr_set = false, have_new = false, have_old = false;
+    bool name_set = false, attr_set = false, sql_set = false, have_new = false, have_old = false;
     bool new_v = false, old_v = false;
     uint32_t new_o = 0, new_l = 0, old_o = 0, old_l = 0;
     uint32_t prev_f = 0;
@@ -107,6 +124,7 @@ __global__ __launch_bounds__(kERec) void enc_span_kernel(EncArgs a) {
       if (!name_set && f >= 5) {
         name_a = a0;
         name_b = f == 5 ? r.i - off : a0;
+        if (f == 5 && wt == 2) own_off = po, own_len = pl;
         name_set = true;
       }
       if (f == 9 && wt == 2) {
@@ -134,6 +152,11 @@ __global__ __launch_bounds__(kERec) void enc_span_kernel(EncArgs a) {
             attr_set = true;
           }
         }
+        if (op && !sql_set && eq_lit(r.br, ko, kl, "db.operation.name", 17)) {
+          sql_a = a0;
+          sql_b = r.i - off;
+          sql_set = true;
+        }
         if (!have_new && eq_lit(r.br, ko, kl, "http.request.method", 19)) {
           have_new = true;
           new_v = hv, new_o = vo, new_l = vl;
@@ -141,9 +164,15 @@ __global__ __launch_bounds__(kERec) void enc_span_kernel(EncArgs a) {
           have_old = true;
           old_v = hv, old_o = vo, old_l = vl;
         }
-      } else if (f > 9 && !attr_set) {
-        attr_a = attr_b = a0;
-        attr_set = true;
+      } else if (f > 9) {
+        if (!attr_set) {
+          attr_a = attr_b = a0;
+          attr_set = true;
+        }
+        if (!sql_set) {
+          sql_a = sql_b = a0;
+          sql_set = true;
+        }
       }
     }
     if (!ok || r.bad || r.i != off + L) {   // re-marshaled, or malformed (the host reports it)
@@ -151,9 +180,10 @@ __global__ __launch_bounds__(kERec) void enc_span_kernel(EncArgs a) {
       continue;
     }
     const bool client = kind == OSE_KIND_CLIENT;
-    if (!(u & OSE_OUT_RENAME)) name_a = name_b = 0;
+    if (!(u & OSE_OUT_RENAME) && !op) name_a = name_b = 0;
     if (!(u & OSE_OUT_SET_ATTR)) attr_a = attr_b = L;
-    uint64_t out = (uint64_t)L - (name_b - name_a) - (attr_b - attr_a);
+    if (!op) sql_a = sql_b = L;
+    uint64_t out = (uint64_t)L - (name_b - name_a) - (attr_b - attr_a) - (sql_b - sql_a);
     uint32_t meth_off = 0, meth_len = 0;
     if (u & OSE_OUT_RENAME) {
       const bool hv = have_new ? new_v : old_v;
@@ -175,19 +205,25 @@ __global__ __launch_bounds__(kERec) void enc_span_kernel(EncArgs a) {
           continue;
         }
       }
-      out += field_len((uint64_t)meth_len + 1 + t.len);
     }
+    if ((u & OSE_OUT_RENAME) || op)
+      out += field_len(((u & OSE_OUT_RENAME) ? (uint64_t)meth_len + 1 + t.len : (uint64_t)own_len) +
+                       (op ? 1 + sql_op_len(op) : 0));
     if (u & OSE_OUT_SET_ATTR) out += field_len(kv_len(client, t.len));
-    if (name_b > attr_a) {   // not the ascending order the plan assumes
+    if (op) out += field_len(sql_kv_len(op));
+    if (name_b > attr_a || name_b > sql_a) {   // not the ascending order the plan assumes
       fb |= kEncFbSpan;
       continue;
     }
     a.edit[i] = EncEdit{name_a, name_b, attr_a, attr_b, meth_off, meth_len, t.off, t.len, (uint32_t)out,
-                        u | (client ? 0x100u : 0u)};
+                        u | (client ? 0x100u : 0u) | (op << 16)};
+    if (kSql) a.sql_edit[i] = EncSqlEdit{sql_a, sql_b, own_off, own_len};
     a.span_out[i] = (uint32_t)field_len(out);
   }
   if (fb) flag(a, fb);
 }
+__global__ __launch_bounds__(kERec) void enc_span_kernel(EncArgs a) { enc_span_body<false>(a); }
+__global__ __launch_bounds__(kERec) void enc_span_sql_kernel(EncArgs a) { enc_span_body<true>(a); }
 
 // ---- sizing: scopes ------------------------------------------------------------
 // Enc::size_chunk's scope loop: header (pdata always writes the
@@ -495,32 +531,62 @@ __device__ __forceinline__ uint64_t uni64(uint64_t x) {
 __device__ __forceinline__ uint32_t uni32(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
 __device__ __forceinline__ uint32_t lane32(uint32_t x, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)x, l); }
 
-// Enc::write_edit
-__device__ void write_edit(const EncArgs& a, WaveOut& w, const uint8_t* sp, uint32_t L, const EncEdit& e) {
+// Enc::write_edit (kSql: with the sql_op part of the plan, q)
+template <bool kSql>
+__device__ void write_edit(const EncArgs& a, WaveOut& w, const uint8_t* sp, uint32_t L, const EncEdit& e,
+                           const EncSqlEdit& q) {
   const uint32_t u = e.flags & 0xFFu;
   const bool client = (e.flags >> 8) & 1u;
-  const uint8_t* T = a.tmpl_arena + e.tmpl_off;
+  const uint32_t op = kSql ? (e.flags >> 16) & 0xFFu : 0u;
+  const uint8_t* T = a.tmpl_arena + e.tmpl_off;   // (not read when tmpl_len is 0: no template stage)
   w.copy(sp, e.name_a);
-  if (u & OSE_OUT_RENAME) {
-    w.hdr(0x2A, (uint64_t)e.meth_len + 1 + e.tmpl_len);
-    w.copy(a.pb + e.meth_off, e.meth_len);
-    w.byte(' ');
-    w.copy(T, e.tmpl_len);
+  if ((u & OSE_OUT_RENAME) || op) {
+    w.hdr(0x2A, ((u & OSE_OUT_RENAME) ? (uint64_t)e.meth_len + 1 + e.tmpl_len : (uint64_t)q.own_len) +
+                    (op ? 1 + sql_op_len(op) : 0));
+    if (u & OSE_OUT_RENAME) {
+      w.copy(a.pb + e.meth_off, e.meth_len);
+      w.byte(' ');
+      w.copy(T, e.tmpl_len);
+    } else {
+      w.copy(a.pb + q.own_off, q.own_len);
+    }
+    if (op) {
+      w.byte(' ');
+      w.lit(sql_op_name(op), sql_op_len(op));
+    }
   }
-  w.copy(sp + e.name_b, e.attr_a - e.name_b);
-  if (u & OSE_OUT_SET_ATTR) {
-    const uint32_t kl = client ? 12 : 10;
-    w.hdr(0x4A, kv_len(client, e.tmpl_len));
-    w.hdr(0x0A, kl);
-    w.lit(client ? "url.template" : "http.route", kl);
-    w.hdr(0x12, field_len(e.tmpl_len));
-    w.hdr(0x0A, e.tmpl_len);
-    w.copy(T, e.tmpl_len);
+  // the two KeyValues in span order: the target first where both are appended
+  // (without kSql: q is {L, L, 0, 0}, the target first and nothing second)
+  const bool sql_first = kSql && q.sql_a < e.attr_a;
+  const uint32_t a1 = sql_first ? q.sql_a : e.attr_a, b1 = sql_first ? q.sql_b : e.attr_b;
+  const uint32_t a2 = sql_first ? e.attr_a : q.sql_a, b2 = sql_first ? e.attr_b : q.sql_b;
+  w.copy(sp + e.name_b, a1 - e.name_b);
+  for (int k = 0; k < 2; k++) {
+    if ((k == 0) == sql_first) {
+      if (op) {
+        w.hdr(0x4A, sql_kv_len(op));
+        w.hdr(0x0A, 17);
+        w.lit("db.operation.name", 17);
+        w.hdr(0x12, field_len(sql_op_len(op)));
+        w.hdr(0x0A, sql_op_len(op));
+        w.lit(sql_op_name(op), sql_op_len(op));
+      }
+    } else if (u & OSE_OUT_SET_ATTR) {
+      const uint32_t kl = client ? 12 : 10;
+      w.hdr(0x4A, kv_len(client, e.tmpl_len));
+      w.hdr(0x0A, kl);
+      w.lit(client ? "url.template" : "http.route", kl);
+      w.hdr(0x12, field_len(e.tmpl_len));
+      w.hdr(0x0A, e.tmpl_len);
+      w.copy(T, e.tmpl_len);
+    }
+    if (k == 0) w.copy(sp + b1, a2 - b1);
   }
-  w.copy(sp + e.attr_b, L - e.attr_b);
+  w.copy(sp + b2, L - b2);
 }
 
 // the record of resource r at dst (Enc::write_chunk)
+template <bool kSql>
 __device__ void write_record(const EncArgs& a, uint64_t r, uint8_t* dst, uint64_t rec) {
   WaveOut w{dst, 0, rec, (int)(threadIdx.x & 63)};
   w.hdr(0x0A, uni64(a.res_body[r]));
@@ -548,7 +614,7 @@ __device__ void write_record(const EncArgs& a, uint64_t r, uint8_t* dst, uint64_
         const uint64_t ref = a.span_ref[j];
         roff = (uint32_t)ref;
         rlen = (uint32_t)(ref >> 32);
-        u = a.url_out ? a.url_out[j] : 0u;
+        u = (a.url_out ? a.url_out[j] : 0u) | (kSql ? (uint32_t)a.sql_op[j] << 8 : 0u);   // 0: verbatim
       }
       uint64_t kept = __ballot(so != 0);
       while (kept) {
@@ -571,8 +637,16 @@ __device__ void write_record(const EncArgs& a, uint64_t r, uint8_t* dst, uint64_
           e.tmpl_len = uni32(ep->tmpl_len);
           e.out_len = uni32(ep->out_len);
           e.flags = uni32(ep->flags);
+          EncSqlEdit q{L, L, 0, 0};
+          if (kSql) {
+            const EncSqlEdit* qp = a.sql_edit + c + (uint64_t)b;
+            q.sql_a = uni32(qp->sql_a);
+            q.sql_b = uni32(qp->sql_b);
+            q.own_off = uni32(qp->own_off);
+            q.own_len = uni32(qp->own_len);
+          }
           w.hdr(0x12, e.out_len);
-          write_edit(a, w, a.pb + off, L, e);
+          write_edit<kSql>(a, w, a.pb + off, L, e, q);
         }
       }
     }
@@ -592,7 +666,8 @@ __device__ void write_record(const EncArgs& a, uint64_t r, uint8_t* dst, uint64_
 }  // namespace
 
 // a wave per resource (grid-stride), its record to every output it routes to
-__global__ __launch_bounds__(kERec) void enc_write_kernel(EncArgs a) {
+template <bool kSql>
+__device__ __forceinline__ void enc_write_body(const EncArgs& a) {
   const uint64_t waves = (uint64_t)gridDim.x * (kERec / kWave);
   for (uint64_t r = uni64((uint64_t)blockIdx.x * (kERec / kWave) + (threadIdx.x >> 6)); r < a.n_res; r += waves) {
     const uint64_t rec = uni64(a.res_rec[r]);
@@ -601,10 +676,12 @@ __global__ __launch_bounds__(kERec) void enc_write_kernel(EncArgs a) {
     while (mask) {
       const uint32_t k = (uint32_t)__builtin_ctzll(mask);
       mask &= mask - 1;
-      write_record(a, r, a.out + a.out_base[k] + uni64(a.off[(uint64_t)k * a.n_res + r]), rec);
+      write_record<kSql>(a, r, a.out + a.out_base[k] + uni64(a.off[(uint64_t)k * a.n_res + r]), rec);
     }
   }
 }
+__global__ __launch_bounds__(kERec) void enc_write_kernel(EncArgs a) { enc_write_body<false>(a); }
+__global__ __launch_bounds__(kERec) void enc_write_sql_kernel(EncArgs a) { enc_write_body<true>(a); }
 
 // ---- launchers ---------------------------------------------------------------------
 namespace {
@@ -616,7 +693,9 @@ inline uint32_t grid_of(uint64_t n, uint32_t cap) {
 }
 }  // namespace
 void launch_enc_spans(const EncArgs& a, hipStream_t st) {
-  if (a.n_spans) hipLaunchKernelGGL(enc_span_kernel, dim3(grid_of(a.n_spans, 8192)), dim3(kERec), 0, st, a);
+  if (!a.n_spans) return;
+  if (a.sql_op) hipLaunchKernelGGL(enc_span_sql_kernel, dim3(grid_of(a.n_spans, 8192)), dim3(kERec), 0, st, a);
+  else hipLaunchKernelGGL(enc_span_kernel, dim3(grid_of(a.n_spans, 8192)), dim3(kERec), 0, st, a);
 }
 void launch_enc_scopes(const EncArgs& a, hipStream_t st) {
   if (a.n_scopes) hipLaunchKernelGGL(enc_scope_kernel, dim3(grid_of(a.n_scopes, ~0u)), dim3(kERec), 0, st, a);
@@ -631,7 +710,9 @@ void launch_enc_scan(const EncArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(enc_scan_apply_kernel, dim3(tiles, a.n_out), dim3(kEThreads), 0, st, a, tiles);
 }
 void launch_enc_write(const EncArgs& a, hipStream_t st) {
-  if (a.n_res) hipLaunchKernelGGL(enc_write_kernel, dim3(grid_of(a.n_res * kWave, 16384)), dim3(kERec), 0, st, a);
+  if (!a.n_res) return;
+  if (a.sql_op) hipLaunchKernelGGL(enc_write_sql_kernel, dim3(grid_of(a.n_res * kWave, 16384)), dim3(kERec), 0, st, a);
+  else hipLaunchKernelGGL(enc_write_kernel, dim3(grid_of(a.n_res * kWave, 16384)), dim3(kERec), 0, st, a);
 }
 
 }  // namespace ose

@@ -948,9 +948,12 @@ int ose_engine_set_option(ose_engine* eng, const char* name, int64_t value) {
       {"otlp_host_resources", Engine::kOptOtlpHostResources},
       {"otlp_host_scopes", Engine::kOptOtlpHostScopes},
       {"encode_host", Engine::kOptEncodeHost},
+      {"otlp_sqlop", Engine::kOptOtlpSqlop},
   };
   for (const auto& o : kOpts) {
     if (strcmp(name, o.name) != 0) continue;
+    if (o.bit == Engine::kOptOtlpSqlop && !e->has_sqlop)
+      return fail(OSE_EINVAL, "engine option otlp_sqlop: odigossqldboperationprocessor is not configured");
     if (value) e->options.fetch_or(o.bit);
     else e->options.fetch_and(~o.bit);
     return 0;

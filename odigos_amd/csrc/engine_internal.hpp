@@ -120,7 +120,11 @@ struct Engine {
   // ose_engine_set_option: alternative implementations of the OTLP legs
   // (the default path is the fast one; these select the others, for tests
   // that compare the two)
-  enum : uint32_t { kOptOtlpGpuChain = 1, kOptOtlpHostResources = 2, kOptOtlpHostScopes = 4, kOptEncodeHost = 8 };
+  // kOptOtlpSqlop is a feature switch, not an alternative leg: the OTLP
+  // path carries odigossqldboperationprocessor (off until the next ABI version)
+  enum : uint32_t {
+    kOptOtlpGpuChain = 1, kOptOtlpHostResources = 2, kOptOtlpHostScopes = 4, kOptEncodeHost = 8, kOptOtlpSqlop = 16
+  };
   std::atomic<uint32_t> options{0};
   bool option(uint32_t o) const { return (options.load(std::memory_order_relaxed) & o) != 0; }
   bool url_needs_resource = false;

@@ -59,10 +59,25 @@ uint64_t mix(uint64_t x) {
   return x ^ (x >> 31);
 }
 const char* kMethod[] = {"GET", "POST", "PUT", "DELETE"};
+// db.query.text of the spans that carry one (osegen_otlp_sql): statements a
+// database instrumentation records, some in lower case or after blanks, one
+// the processor does not know
+const char* kQuery[] = {
+    "SELECT id, name, email FROM users WHERE id = ?",
+    "select * from orders o join items i on i.order_id = o.id where o.customer_id = ? order by o.created_at desc limit 50",
+    "INSERT INTO events (id, kind, payload, created_at) VALUES (?, ?, ?, now())",
+    "  UPDATE accounts SET balance = balance - ? WHERE id = ?",
+    "DELETE FROM sessions WHERE expires_at < ?",
+    "\n\tSELECT count(*) FROM audit_log WHERE tenant = ? AND at > ?",
+    "EXPLAIN ANALYZE SELECT 1",
+    "CREATE INDEX idx_items_order ON items (order_id)",
+};
 
 struct Res { uint64_t first, count; };
 
-void encode_resources(const ose_columns* c, const std::vector<Res>& res, size_t r0, size_t r1, std::string& out) {
+// sql_every != 0: one span in sql_every also carries a db.query.text (its last attribute)
+void encode_resources(const ose_columns* c, const std::vector<Res>& res, size_t r0, size_t r1, std::string& out,
+                      uint32_t sql_every) {
   std::string rs, sc, sp, tmp;
   for (size_t r = r0; r < r1; r++) {
     rs.clear();
@@ -132,6 +147,10 @@ void encode_resources(const ose_columns* c, const std::vector<Res>& res, size_t 
         kv_str(sp, 9, "network.protocol.version", "1.1", 3);
         kv_str(sp, 9, "user_agent.original", kUa, sizeof kUa - 1);
       }
+      if (sql_every && mix(h ^ 0x5C1) % sql_every == 0) {
+        const char* q = kQuery[mix(h ^ 0xD8) % (sizeof kQuery / sizeof kQuery[0])];
+        kv_str(sp, 9, "db.query.text", q, std::strlen(q));
+      }
       {   // Status: non-nullable, always framed
         std::string st;
         if (c->status[i]) {
@@ -153,8 +172,9 @@ extern "C" {
 
 // TracesData bytes of the batch `cols` (as osegen_columns returns it: spans
 // in resource order, one scope per resource).  *len receives the size;
-// free with osegen_otlp_free.
-char* osegen_otlp(const ose_columns* c, int threads, uint64_t* len) {
+// free with osegen_otlp_free.  osegen_otlp_sql: the same with a db.query.text
+// on one span in sql_every (0: none), for the odigossqldboperationprocessor legs.
+char* osegen_otlp_sql(const ose_columns* c, int threads, uint64_t* len, uint32_t sql_every) {
   std::vector<Res> res(c->n_resources, Res{0, 0});
   for (uint64_t i = 0; i < c->n_spans; i++) {
     const uint32_t r = c->resource[i];
@@ -166,7 +186,7 @@ char* osegen_otlp(const ose_columns* c, int threads, uint64_t* len) {
   std::vector<std::string> parts((size_t)threads);
   std::vector<std::thread> th;
   for (int t = 0; t < threads; t++)
-    th.emplace_back([&, t]() { encode_resources(c, res, R * t / threads, R * (t + 1) / threads, parts[t]); });
+    th.emplace_back([&, t]() { encode_resources(c, res, R * t / threads, R * (t + 1) / threads, parts[t], sql_every); });
   for (auto& x : th) x.join();
   uint64_t total = 0;
   for (auto& p : parts) total += p.size();
@@ -179,6 +199,8 @@ char* osegen_otlp(const ose_columns* c, int threads, uint64_t* len) {
   *len = total;
   return out;
 }
+
+char* osegen_otlp(const ose_columns* c, int threads, uint64_t* len) { return osegen_otlp_sql(c, threads, len, 0); }
 
 void osegen_otlp_free(char* p) { std::free(p); }
 

@@ -593,7 +593,7 @@ struct ResSlotDev {          // 48 B; ready != 0: filled
   uint32_t koff, klen;       // key bytes in the table's key arena
   uint32_t svc, svc_str, set, rpart;
   uint64_t attr_res;
-  uint32_t ok, ready;
+  uint32_t ok, ready;        // ok: bit 0 res_url_ok, bit 1 res_sql_ok
 };
 constexpr uint32_t kResSlots = 1u << 17;
 constexpr uint32_t kResKeyBytes = 16u << 20;
@@ -619,6 +619,7 @@ struct OtlpResArgs {
   uint32_t* res_set;           // the resource cache's attribute-set id (batch ids after compaction)
   uint32_t* res_size;
   uint8_t* res_ok;
+  uint8_t* res_sql_ok;         // may be null (engine option otlp_sqlop off)
   uint64_t* attr_res;
   uint32_t* miss_count;        // [1]
   uint32_t* miss_list;         // [n_res]
@@ -652,6 +653,7 @@ void launch_otlp_chain_list(const OtlpChainArgs& a, hipStream_t st);
 void launch_otlp_res_fields(const OtlpResArgs& a, hipStream_t st);
 void launch_otlp_res_scopes(const OtlpResArgs& a, hipStream_t st);
 // the host's columns of the missed resources: fix k = {row, svc, svc_str, set, rpart, ok, attr_res}
+// (ok as in ResSlotDev: bit 0 res_url_ok, bit 1 res_sql_ok)
 struct OtlpResFix {
   uint32_t row, svc, svc_str, set, rpart, ok;
   uint64_t attr_res;
@@ -693,7 +695,17 @@ struct EncEdit {        // one rewritten span (otlp_encode.cpp Edit)
   uint32_t meth_off, meth_len;   // the method string in the message
   uint32_t tmpl_off, tmpl_len;   // the template in the template arena
   uint32_t out_len;              // edited span bytes
-  uint32_t flags;                // url_out | client << 8
+  uint32_t flags;                // url_out | client << 8 | sql_op << 16
+};
+// ... and what a sql_op adds to the plan (a call with OSE_STAGE_SQLOP /
+// OSE_STAGE_APPLY_SQLOP; kernels of their own, so a call without runs the
+// code it ran before): the db.operation.name KeyValue replaced (sql_a <
+// sql_b) or inserted (sql_a == sql_b), and the span's own name (field 5's
+// payload, in the message), which the new name starts with unless the URL
+// stage renamed the span
+struct EncSqlEdit {
+  uint32_t sql_a, sql_b;
+  uint32_t own_off, own_len;
 };
 struct EncRouteSlot {   // router key "ns/kind/name" -> pipelines; klen == ~0: empty
   uint64_t h;
@@ -710,6 +722,8 @@ struct EncArgs {
   const ose_strref* tmpl;
   const uint8_t* tmpl_arena;
   const uint64_t* tmpl_used;
+  const uint8_t* sql_op;         // NULL: no odigossqldboperationprocessor stage
+  EncSqlEdit* sql_edit;          // [n_spans] with sql_op
   const uint32_t* scope_span0;
   const uint64_t* scope_hdr;     // InstrumentationScope ref (0: none, kOtlpScopeMulti: merged)
   const uint64_t* scope_schema;
@@ -776,6 +790,31 @@ struct OtlpFixArgs {
 };
 void launch_otlp_spans(const OtlpArgs& a, hipStream_t st);
 void launch_otlp_fix(const OtlpFixArgs& a, hipStream_t st);
+
+// odigossqldboperationprocessor's span columns from the message
+// (otlp_sqlop_kernel.hip; engine option otlp_sqlop).  A pass of its own after
+// the span kernel, one lane per span: db_flags, and db_query as a ref into
+// the message bytes when db.query.text is a string_value.  Any other value
+// needs AsString: the span joins the host pass's list (unless the span kernel
+// listed it already), and the host pass writes both columns of every listed
+// span (OtlpSqlFix, after OtlpFix).
+struct OtlpSqlArgs {
+  const uint8_t* pb;            // as OtlpArgs::pb
+  uint64_t n_spans;
+  const uint64_t* span_ref;
+  uint8_t* db_flags;
+  ose_strref* db_query;
+  uint8_t* host_flag;           // the span kernel's; 1: skipped here
+  uint32_t* host_count;
+  uint32_t* host_list;
+  uint32_t host_cap;
+};
+void launch_otlp_sqlop(const OtlpSqlArgs& a, hipStream_t st);
+struct OtlpSqlFix {
+  uint32_t idx, flags;
+  ose_strref query;
+};
+void launch_otlp_sqlop_fix(const OtlpSqlFix* fix, uint32_t n, uint8_t* db_flags, ose_strref* db_query, hipStream_t st);
 
 // ---- groupbytrace store (gbt_kernel.hip) --------------------------------------
 struct GbtSlot {              // trace id -> creation number (32 B, generation-tagged)

@@ -1,6 +1,6 @@
 // otlp_encode.cpp — the gateway's output side: the
-// decisions the GPU made on a decoded OTLP batch (keep, url_out + template)
-// applied to the message bytes, the resources routed to the data-stream
+// decisions the GPU made on a decoded OTLP batch (keep, url_out + template,
+// sql_op) applied to the message bytes, the resources routed to the data-stream
 // pipelines as odigosrouterconnector does, and one serialized TracesData
 // written per pipeline — what the exporters behind each pipeline marshal.
 //
@@ -11,6 +11,8 @@
 //   * a renamed / templated span of that kind is edited in place: the name
 //     field replaced or inserted, the target attribute's KeyValue replaced
 //     (Map.PutStr on an existing key) or appended after the last attribute;
+//     odigossqldboperationprocessor's db.operation.name is put the same way
+//     after it, and " " + NAME ends the name;
 //   * any other span (an encoding pdata would not write: unknown fields,
 //     unframed empty ids, non-minimal varints) is decoded and re-marshaled.
 // Resource and scope headers are re-marshaled from their decoded form
@@ -199,7 +201,17 @@ struct Edit {
   uint32_t tmpl_off, tmpl_len;   // the template (in the template arena)
   uint32_t out_len;
   uint8_t u, client, in_mods, meth_in_mods;
+  // odigossqldboperationprocessor (op != 0): the db.operation.name KeyValue
+  // replaced (sql_a < sql_b) or inserted (sql_a == sql_b), and the span's own
+  // name (the payload of field 5, in the span) the new name starts with
+  // unless the URL stage renamed the span
+  uint32_t sql_a, sql_b, own_off, own_len;
+  uint8_t op;
 };
+
+// the constants of odigossqldboperationprocessor/processor.go:19-27, by OSE_SQLOP_*
+const char* const kSqlOpName[8] = {"", "SELECT", "INSERT", "UPDATE", "DELETE", "CREATE", "DROP", "ALTER"};
+inline size_t sql_op_len(uint8_t op) { return op == OSE_SQLOP_DROP ? 4 : op == OSE_SQLOP_ALTER ? 5 : 6; }
 
 struct Chunk {
   size_t r0 = 0, r1 = 0;
@@ -237,7 +249,8 @@ struct Enc {
   }
   bool kept(uint64_t i) const { return !d.keep || d.keep[i]; }
   bool rewritten(uint64_t i) const {
-    return (d.url_out && d.url_out[i]) || (d.span_size && d.span_size[i] != (uint32_t)(span_ref[i] >> 32));
+    return (d.url_out && d.url_out[i]) || (d.sql_op && d.sql_op[i]) ||
+           (d.span_size && d.span_size[i] != (uint32_t)(span_ref[i] >> 32));
   }
   void outputs_of(const ResHdr* h, uint32_t* ks, uint32_t& nk) const {
     nk = 0;
@@ -316,17 +329,21 @@ struct Enc {
       if ((uint64_t)t.off + t.len > d.tmpl_arena_len) { c.err = "template reference beyond the template arena"; return false; }
       T = std::string_view((const char*)d.tmpl_arena + t.off, t.len);
     }
+    const uint8_t op = d.sql_op ? d.sql_op[i] : 0;
+    if (op > OSE_SQLOP_ALTER) { c.err = "sql_op beyond OSE_SQLOP_ALTER"; return false; }
     const bool canonical = !d.span_size || d.span_size[i] == (uint32_t)L;
     if (canonical) {
-      int rc = plan_edit(c, sp, L, u, T);
+      int rc = plan_edit(c, sp, L, u, T, op);
       if (rc < 0) return false;
       if (rc > 0) return true;
     }
-    return remarshal(c, sp, L, u, T);
+    return remarshal(c, sp, L, u, T, op);
   }
 
-  // host.cpp Apply (processor.go:230-232, 259) on the decoded span, written to c.mods
-  bool remarshal(Chunk& c, const uint8_t* sp, size_t L, uint8_t u, std::string_view T) {
+  // host.cpp Apply (odigosurltemplate processor.go:230-232, 259, then
+  // odigossqldboperationprocessor processor.go:68-72) on the decoded span,
+  // written to c.mods
+  bool remarshal(Chunk& c, const uint8_t* sp, size_t L, uint8_t u, std::string_view T, uint8_t op) {
     Span s;
     if (!pb_span(sp, L, s)) { c.err = "OTLP protobuf: malformed Span"; return false; }
     if (u) {
@@ -337,6 +354,10 @@ struct Enc {
         if (!m) m = s.attrs.Get("http.method");
         s.name = (m ? m->AsString() : std::string()) + " " + tmpl;
       }
+    }
+    if (op) {
+      s.attrs.PutStr("db.operation.name", kSqlOpName[op]);
+      s.name = s.name + " " + kSqlOpName[op];
     }
     const size_t start = c.mods.size();
     ProtoWriter(c.mods).span(s);
@@ -351,13 +372,18 @@ struct Enc {
   // The same change on bytes already in pdata's encoding, as a plan: fields
   // ascend, so the new name takes field 5's place (or goes before the first
   // later field) and the target KeyValue replaces the first one with its key
-  // (Map.PutStr) or goes after the last attribute.  1 = planned, 0 = the
-  // fields are out of order (re-marshal), -1 = malformed.
-  int plan_edit(Chunk& c, const uint8_t* sp, size_t L, uint8_t u, std::string_view T) {
+  // (Map.PutStr) or goes after the last attribute.  With op, the name also
+  // gets " " + NAME (after the URL stage's name, or the span's own) and
+  // db.operation.name is put the same way, after an appended target KeyValue.
+  // 1 = planned, 0 = the fields are out of order (re-marshal), -1 = malformed.
+  int plan_edit(Chunk& c, const uint8_t* sp, size_t L, uint8_t u, std::string_view T, uint8_t op) {
     Edit e{};
     e.u = u;
+    e.op = op;
     e.name_a = e.name_b = (uint32_t)L;
     e.attr_a = e.attr_b = (uint32_t)L;
+    e.sql_a = e.sql_b = (uint32_t)L;
+    bool sql_set = false;
     e.tmpl_off = (uint32_t)(T.data() - (const char*)d.tmpl_arena);
     e.tmpl_len = (uint32_t)T.size();
     int32_t kind = 0;
@@ -383,6 +409,7 @@ struct Enc {
       if (!name_set && f >= 5) {   // the name's place
         e.name_a = (uint32_t)a;
         e.name_b = f == 5 ? (uint32_t)r.i : (uint32_t)a;
+        if (f == 5 && wt == 2) e.own_off = (uint32_t)po, e.own_len = (uint32_t)pl;
         name_set = true;
       }
       if (f == 9 && wt == 2) {
@@ -411,6 +438,11 @@ struct Enc {
             attr_set = true;
           }
         }
+        if (op && !sql_set && kl == 17 && std::memcmp(key, "db.operation.name", 17) == 0) {
+          e.sql_a = (uint32_t)a;
+          e.sql_b = (uint32_t)r.i;
+          sql_set = true;
+        }
         if (!have_new && kl == 19 && std::memcmp(key, "http.request.method", 19) == 0) {
           have_new = true;
           mnew = hv ? sp + po + vo : nullptr, mnew_len = hv ? vl : 0;
@@ -418,16 +450,23 @@ struct Enc {
           have_old = true;
           mold = hv ? sp + po + vo : nullptr, mold_len = hv ? vl : 0;
         }
-      } else if (f > 9 && !attr_set) {   // after the last attribute
-        e.attr_a = e.attr_b = (uint32_t)a;
-        attr_set = true;
+      } else if (f > 9) {   // after the last attribute
+        if (!attr_set) {
+          e.attr_a = e.attr_b = (uint32_t)a;
+          attr_set = true;
+        }
+        if (!sql_set) {
+          e.sql_a = e.sql_b = (uint32_t)a;
+          sql_set = true;
+        }
       }
     }
     if (!r.ok || r.i != L) { c.err = "OTLP protobuf: malformed Span"; return -1; }
     e.client = kind == OSE_KIND_CLIENT;
-    if (!(u & OSE_OUT_RENAME)) e.name_a = e.name_b = 0;
+    if (!(u & OSE_OUT_RENAME) && !op) e.name_a = e.name_b = 0;
     if (!(u & OSE_OUT_SET_ATTR)) e.attr_a = e.attr_b = (uint32_t)L;
-    uint64_t out = L - (e.name_b - e.name_a) - (e.attr_b - e.attr_a);
+    if (!op) e.sql_a = e.sql_b = (uint32_t)L;
+    uint64_t out = L - (e.name_b - e.name_a) - (e.attr_b - e.attr_a) - (e.sql_b - e.sql_a);
     if (u & OSE_OUT_RENAME) {
       // the method: AnyValue{string_value} in place; anything else through pdata's AsString
       const uint8_t* mv = have_new ? mnew : mold;
@@ -455,16 +494,23 @@ struct Enc {
           c.mods += m;
         }
       }
-      out += flen((uint64_t)e.meth_len + 1 + T.size());
     }
+    if ((u & OSE_OUT_RENAME) || op) out += flen(new_name_len(e));
     if (u & OSE_OUT_SET_ATTR) out += flen(kv_len(e.client, T.size()));
-    if (e.name_b > e.attr_a) return 0;   // not the ascending order the plan assumes
+    if (op) out += flen(sql_kv_len(op));
+    if (e.name_b > e.attr_a || e.name_b > e.sql_a) return 0;   // not the ascending order the plan assumes
     e.out_len = (uint32_t)out;
     c.edits.push_back(e);
     return 1;
   }
   static uint64_t kv_len(bool client, size_t tl) {   // KeyValue{key, AnyValue{string_value}}
     return flen(client ? 12 : 10) + flen(flen(tl));
+  }
+  static uint64_t sql_kv_len(uint8_t op) { return flen(17) + flen(flen(sql_op_len(op))); }
+  // the edited name: the URL stage's (method + " " + template) or the span's own, then " " + NAME
+  static uint64_t new_name_len(const Edit& e) {
+    const uint64_t base = (e.u & OSE_OUT_RENAME) ? (uint64_t)e.meth_len + 1 + e.tmpl_len : e.own_len;
+    return base + (e.op ? 1 + sql_op_len(e.op) : 0);
   }
 
   // an edited span's bytes at w
@@ -476,18 +522,58 @@ struct Enc {
     const char* T = (const char*)d.tmpl_arena + e.tmpl_off;
     std::memcpy(w, sp, e.name_a);
     w += e.name_a;
-    if (e.u & OSE_OUT_RENAME) {
+    if ((e.u & OSE_OUT_RENAME) || e.op) {
       *w++ = 0x2A;
-      w = put_varint(w, (uint64_t)e.meth_len + 1 + e.tmpl_len);
-      const uint8_t* m = e.meth_in_mods ? (const uint8_t*)c.mods.data() + e.meth_off : pb + e.meth_off;
-      std::memcpy(w, m, e.meth_len);
-      w += e.meth_len;
-      *w++ = ' ';
-      std::memcpy(w, T, e.tmpl_len);
-      w += e.tmpl_len;
+      w = put_varint(w, new_name_len(e));
+      if (e.u & OSE_OUT_RENAME) {
+        const uint8_t* m = e.meth_in_mods ? (const uint8_t*)c.mods.data() + e.meth_off : pb + e.meth_off;
+        std::memcpy(w, m, e.meth_len);
+        w += e.meth_len;
+        *w++ = ' ';
+        std::memcpy(w, T, e.tmpl_len);
+        w += e.tmpl_len;
+      } else {
+        std::memcpy(w, sp + e.own_off, e.own_len);
+        w += e.own_len;
+      }
+      if (e.op) {
+        *w++ = ' ';
+        std::memcpy(w, kSqlOpName[e.op], sql_op_len(e.op));
+        w += sql_op_len(e.op);
+      }
     }
-    std::memcpy(w, sp + e.name_b, e.attr_a - e.name_b);
-    w += e.attr_a - e.name_b;
+    // the two KeyValues in span order: the target first where both are appended
+    const bool sql_first = e.sql_a < e.attr_a;
+    const uint32_t a1 = sql_first ? e.sql_a : e.attr_a, b1 = sql_first ? e.sql_b : e.attr_b;
+    const uint32_t a2 = sql_first ? e.attr_a : e.sql_a, b2 = sql_first ? e.attr_b : e.sql_b;
+    std::memcpy(w, sp + e.name_b, a1 - e.name_b);
+    w += a1 - e.name_b;
+    if (sql_first) w = write_sql_kv(e, w);
+    else w = write_tmpl_kv(e, T, w);
+    std::memcpy(w, sp + b1, a2 - b1);
+    w += a2 - b1;
+    if (sql_first) w = write_tmpl_kv(e, T, w);
+    else w = write_sql_kv(e, w);
+    std::memcpy(w, sp + b2, L - b2);
+    return w + (L - b2);
+  }
+  static uint8_t* write_sql_kv(const Edit& e, uint8_t* w) {
+    if (!e.op) return w;
+    const size_t ol = sql_op_len(e.op);
+    *w++ = 0x4A;
+    w = put_varint(w, sql_kv_len(e.op));
+    *w++ = 0x0A;
+    *w++ = 17;
+    std::memcpy(w, "db.operation.name", 17);
+    w += 17;
+    *w++ = 0x12;
+    *w++ = (uint8_t)flen(ol);
+    *w++ = 0x0A;
+    *w++ = (uint8_t)ol;
+    std::memcpy(w, kSqlOpName[e.op], ol);
+    return w + ol;
+  }
+  static uint8_t* write_tmpl_kv(const Edit& e, const char* T, uint8_t* w) {
     if (e.u & OSE_OUT_SET_ATTR) {
       const size_t kl = e.client ? 12 : 10;
       *w++ = 0x4A;
@@ -503,8 +589,7 @@ struct Enc {
       std::memcpy(w, T, e.tmpl_len);
       w += e.tmpl_len;
     }
-    std::memcpy(w, sp + e.attr_b, L - e.attr_b);
-    return w + (L - e.attr_b);
+    return w;
   }
 
   // pass 1: sizes, headers, edited spans

@@ -56,6 +56,7 @@ struct EncodeDecisions {
   const uint8_t* tmpl_arena = nullptr;
   uint64_t tmpl_arena_len = 0;
   const uint32_t* span_size = nullptr;  // pdata's size of each span (NULL: trust the input's encoding)
+  const uint8_t* sql_op = nullptr;      // OSE_SQLOP_* per span (NULL: no odigossqldboperationprocessor stage)
 };
 
 struct EncodedOutput {

@@ -7,9 +7,12 @@
 //      contents, one header per span);
 //   2. per-resource and per-scope columns on the host (columnize.cpp: the
 //      service ids, include/exclude, attribute sets, the fixed sizes);
-//   3. otlp_span_kernel decodes every span on the GPU;
-//   4. the spans it lists get the host pass: pb_span + columnize_span, their
-//      strings appended after the message bytes, written by otlp_fix_kernel.
+//   3. otlp_span_kernel decodes every span on the GPU; under the engine option
+//      otlp_sqlop, otlp_sqlop_kernel then reads db.query.text /
+//      db.operation.name (db_flags, db_query) and may add spans to the list;
+//   4. the spans they list get the host pass: pb_span + columnize_span, their
+//      strings appended after the message bytes, written by otlp_fix_kernel
+//      (and otlp_sqlop_fix_kernel).
 #include <algorithm>
 #include <chrono>
 #include <deque>
@@ -64,6 +67,7 @@ struct CachedRes {
   uint32_t svc, svc_str, set, rpart;   // set: id in ResCache::sets
   uint8_t ok;
   uint64_t attr_res;
+  uint8_t sql_ok;   // !shouldExcludeLanguage (1 on an engine without odigossqldboperationprocessor)
 };
 
 // Resource columns by message bytes, kept across calls (a gateway sees the
@@ -127,7 +131,7 @@ struct DevResTable {
         e.set = cr.set;
         e.rpart = cr.rpart;
         e.attr_res = cr.attr_res;
-        e.ok = cr.ok;
+        e.ok = (uint32_t)cr.ok | ((uint32_t)cr.sql_ok << 1);
         e.ready = 1;
         changed.push_back(slot);
         n++;
@@ -225,7 +229,7 @@ OtlpEngine* otlp_engine(Engine* e, int& rc) {
   if (e->otlp) return e->otlp;
   auto* o = new OtlpEngine();
   o->err = o->ctx.build(e->has_url ? &e->url : nullptr, e->has_sampling ? &e->sampling : nullptr,
-                        e->has_traffic ? &e->traffic : nullptr);
+                        e->has_traffic ? &e->traffic : nullptr, e->has_sqlop ? &e->sqlop : nullptr);
   if (!o->err.empty()) { rc = fail(OSE_EINVAL, o->err); delete o; return nullptr; }
   std::map<std::string, uint64_t> roles;
   roles["http.request.method"] |= kRoleMethodNew;
@@ -315,7 +319,7 @@ struct Walked {
   std::vector<uint32_t> scope_count;
   std::vector<uint32_t> span_res, span_scope;
   std::vector<uint32_t> res_svc, res_svc_str, res_attrset, res_size, scope_size, scope_res;
-  std::vector<uint8_t> res_ok;
+  std::vector<uint8_t> res_ok, res_sql_ok;
   std::vector<uint64_t> attr_res;
   std::vector<std::vector<std::pair<std::string, std::string>>> sets;
   OtlpLayout lay;   // what the re-encoder needs (otlp_encode.cpp)
@@ -325,7 +329,7 @@ struct WalkChunk {
   std::vector<uint64_t> span_ref;
   std::vector<uint32_t> span_res, span_scope;   // chunk-local indices
   std::vector<uint32_t> res_svc, res_svc_str, res_set, res_size, scope_size, scope_res;
-  std::vector<uint8_t> res_ok;
+  std::vector<uint8_t> res_ok, res_sql_ok;
   std::vector<uint64_t> attr_res;
   OtlpLayout lay;   // res_scope0 / scope_span0 chunk-local
   // GPU-walked scopes (walk with gpu_scopes): span_ref lists only the spans
@@ -373,6 +377,7 @@ bool resolve_resource(const ColumnizeCtx& ctx, ResCache& cache, const uint8_t* p
   cr.svc = rc.svc;
   cr.svc_str = rc.svc_str;
   cr.ok = rc.url_ok;
+  cr.sql_ok = rc.sql_ok;
   cr.attr_res = host_rule_word(ctx.attr_plan, rc.attr_res);   // <= 64 json rules (otlp_engine)
   cr.rpart = (uint32_t)flen(sizer.attrs(attrs, 1) + (dropped ? 1 + sov64(dropped) : 0));   // Resource: always emitted
   const std::string_view key = resf.size() == 1 ? std::string_view((const char*)p + resf[0].first, resf[0].second)
@@ -474,6 +479,7 @@ void walk_segment(const ColumnizeCtx& ctx, ResCache& cache, const uint8_t* p, si
     c.res_svc.push_back(cr.svc);
     c.res_svc_str.push_back(cr.svc_str);
     c.res_ok.push_back(cr.ok);
+    c.res_sql_ok.push_back(cr.sql_ok);
     c.attr_res.push_back(cr.attr_res);
     c.res_set.push_back(cr.set);
     c.res_size.push_back(cr.rpart + (uint32_t)(schema ? flen(schema) : 0));
@@ -675,6 +681,7 @@ bool walk(const ColumnizeCtx& ctx, ResCache& cache, const uint8_t* p, size_t n, 
   w.res_attrset.resize(nres);
   w.res_size.resize(nres);
   w.res_ok.resize(nres);
+  w.res_sql_ok.resize(nres);
   w.attr_res.resize(nres);
   w.scope_size.resize(nscope);
   w.scope_res.resize(nscope);
@@ -705,6 +712,7 @@ bool walk(const ColumnizeCtx& ctx, ResCache& cache, const uint8_t* p, size_t n, 
       w.res_attrset[ro[t] + k] = set_map.at(c.res_set[k]);
       w.res_size[ro[t] + k] = c.res_size[k];
       w.res_ok[ro[t] + k] = c.res_ok[k];
+      w.res_sql_ok[ro[t] + k] = c.res_sql_ok[k];
       w.attr_res[ro[t] + k] = c.attr_res[k];
       w.lay.res_ref[ro[t] + k] = c.lay.res_ref[k];
       w.lay.res_scope0[ro[t] + k] = (uint32_t)(co[t] + c.lay.res_scope0[k]);
@@ -742,7 +750,7 @@ namespace {
 // msg_in_stage: the message's H2D copy reads b->stage (a pageable caller
 // buffer went through it), so the stage is reused only after that copy
 int res_walk_gpu(OtlpEngine* o, OtlpBatchImpl* b, const uint8_t* pb, size_t len, hipStream_t st, Walked& w,
-                 uint64_t* R_out, uint64_t* S_out, OtlpResArgs* args, bool* redo, bool msg_in_stage) {
+                 uint64_t* R_out, uint64_t* S_out, OtlpResArgs* args, bool* redo, bool msg_in_stage, bool sql) {
   *redo = false;
   std::string err;
   int rc;
@@ -831,7 +839,8 @@ int res_walk_gpu(OtlpEngine* o, OtlpBatchImpl* b, const uint8_t* pb, size_t len,
       {(void**)&a.res_ref, 8 * RN}, {(void**)&a.flags, 4 * RN}, {(void**)&a.nscope, 4 * RN},
       {(void**)&a.schema_len, 4 * RN}, {(void**)&a.scope0, 4 * RN}, {(void**)&a.res_svc, 4 * RN},
       {(void**)&a.res_svc_str, 4 * RN}, {(void**)&a.res_set, 4 * RN}, {(void**)&a.res_size, 4 * RN},
-      {(void**)&a.res_ok, RN}, {(void**)&a.attr_res, 8 * RN}, {(void**)&a.miss_list, 4 * RN},
+      {(void**)&a.res_ok, RN}, {(void**)&a.res_sql_ok, sql ? RN : 0}, {(void**)&a.attr_res, 8 * RN},
+      {(void**)&a.miss_list, 4 * RN},
       {(void**)&status, 8 * (size_t)tiles + 64}, {(void**)&words, 64},
   };
   size_t total = 0;
@@ -842,6 +851,7 @@ int res_walk_gpu(OtlpEngine* o, OtlpBatchImpl* b, const uint8_t* pb, size_t len,
     *p.dst = b->rslab.p + off;
     off = up(off + p.bytes + 16);
   }
+  if (!sql) a.res_sql_ok = nullptr;
   if (gpu_chain) {   // the records of the linked segments, written on the GPU
     std::memcpy(b->stage.p, seg_first.data(), 8 * (size_t)T);
     std::memcpy(b->stage.p + 8 * (size_t)T, seg_base.data(), 4 * (size_t)T);
@@ -940,7 +950,7 @@ int res_walk_gpu(OtlpEngine* o, OtlpBatchImpl* b, const uint8_t* pb, size_t len,
           errs[t] = "OTLP protobuf: malformed Resource";
           return;
         }
-        fix[k] = OtlpResFix{r, cr.svc, cr.svc_str, cr.set, cr.rpart, cr.ok, cr.attr_res};
+        fix[k] = OtlpResFix{r, cr.svc, cr.svc_str, cr.set, cr.rpart, (uint32_t)cr.ok | ((uint32_t)cr.sql_ok << 1), cr.attr_res};
         if (resf.size() <= 1) {
           keyed[k] = 1;
           key_of[k] = resf.empty() ? std::pair<size_t, size_t>(0, 0) : resf[0];
@@ -959,7 +969,8 @@ int res_walk_gpu(OtlpEngine* o, OtlpBatchImpl* b, const uint8_t* pb, size_t len,
       std::unique_lock<std::shared_mutex> g(t.mu);
       for (uint32_t k = 0; k < nm; k++) {
         if (!keyed[k]) continue;
-        const CachedRes cr{fix[k].svc, fix[k].svc_str, fix[k].set, fix[k].rpart, (uint8_t)fix[k].ok, fix[k].attr_res};
+        const CachedRes cr{fix[k].svc, fix[k].svc_str, fix[k].set, fix[k].rpart, (uint8_t)(fix[k].ok & 1), fix[k].attr_res,
+                           (uint8_t)(fix[k].ok >> 1)};
         t.insert(pb + key_of[k].first, (uint32_t)key_of[k].second, cr);
       }
       if ((rc = t.sync(st))) return rc;
@@ -1206,6 +1217,8 @@ int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchIm
     t0 = t;
   };
   for (double& x : b->t_ms) x = 0;
+  // engine option otlp_sqlop: db_flags / db_query / res_sql_ok are decoded too
+  const bool sql = e->has_sqlop && e->option(Engine::kOptOtlpSqlop);
   // 1. the bytes H2D (straight from the caller's buffer when it is pinned,
   //    else through pinned staging), the walk meanwhile
   const size_t pb_cap = up(len + 16, 16);
@@ -1235,7 +1248,7 @@ int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchIm
   uint64_t R = 0, S = 0;
   if (gpu_res) {
     bool redo = false;
-    if ((rc = res_walk_gpu(o, b, pb, len, st, w, &R, &S, &ra, &redo, !pinned))) return rc;
+    if ((rc = res_walk_gpu(o, b, pb, len, st, w, &R, &S, &ra, &redo, !pinned, sql))) return rc;
     if (redo) return decode(e, pb, len, st, b, false, true);   // a malformed record: the host walk reports it
   } else {
     if (!walk(o->ctx, o->res_cache, pb, len, w, gpu_scopes)) return fail(OSE_EINVAL, w.err);
@@ -1291,6 +1304,7 @@ int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchIm
     parts.push_back({(void**)&c.res_url_ok, R, w.res_ok.data()});
     parts.push_back({(void**)&c.res_attrset, 4 * R, w.res_attrset.data()});
     parts.push_back({(void**)&c.res_size, 4 * R, w.res_size.data()});
+    if (sql) parts.push_back({(void**)&c.res_sql_ok, R, w.res_sql_ok.data()});
   }
   if (!gpu_scopes) {
     parts.push_back({(void**)&c.scope_size, 4 * S, w.scope_size.data()});
@@ -1314,6 +1328,10 @@ int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchIm
   };
   parts.insert(parts.end(), outs.begin(), outs.end());
   if (o->json_rules) parts.push_back({(void**)&c.attr_match, 8 * N * (size_t)o->attr_words, nullptr});
+  if (sql) {
+    parts.push_back({(void**)&c.db_flags, N, nullptr});
+    parts.push_back({(void**)&c.db_query, 8 * N, nullptr});
+  }
   if (K) {
     parts.push_back({(void**)&c.attr_type, (size_t)K * N, nullptr});
     parts.push_back({(void**)&c.attr_val, 8 * (size_t)K * N, nullptr});
@@ -1338,6 +1356,7 @@ int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchIm
     c.res_url_ok = ra.res_ok;
     c.res_attrset = ra.res_set;
     c.res_size = ra.res_size;
+    c.res_sql_ok = ra.res_sql_ok;
   }
   if (gpu_scopes) {
     c.scope_size = keep_scope.scope_size;
@@ -1399,6 +1418,23 @@ int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchIm
   if (n) launch_otlp_spans(a, st);
   HIP_TRY(hipGetLastError());
   e->prof_end(tm, st);
+  if (sql && n) {   // db_flags / db_query: a pass of its own (the span kernels stay within their register budget)
+    OtlpSqlArgs qa{};
+    qa.pb = b->arena.p;
+    qa.n_spans = n;
+    qa.span_ref = span_ref;
+    qa.db_flags = const_cast<uint8_t*>(c.db_flags);
+    qa.db_query = const_cast<ose_strref*>(c.db_query);
+    qa.host_flag = host_flag;
+    qa.host_count = host_count;
+    qa.host_list = host_list;
+    qa.host_cap = (uint32_t)N;
+    Engine::Timed tq{};
+    e->prof_begin("otlp_sqlop_kernel", st, tq);
+    launch_otlp_sqlop(qa, st);
+    HIP_TRY(hipGetLastError());
+    e->prof_end(tq, st);
+  }
   // 4. the host pass
   uint32_t cnt = 0;
   HIP_TRY(hipMemcpyAsync(&cnt, host_count, 4, hipMemcpyDeviceToHost, st));
@@ -1434,6 +1470,7 @@ int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchIm
   std::vector<uint64_t> fix_val((size_t)cnt * K);
   const uint32_t AW = o->json_rules ? o->attr_words : 0;   // attr_match words the host pass writes per span
   std::vector<uint64_t> fix_attr((size_t)cnt * AW);
+  std::vector<OtlpSqlFix> fix_sql(sql ? cnt : 0);   // db_flags / db_query (AsString included) of the listed spans
   std::string strs;   // appended after the message bytes
   const size_t str_base = pb_cap;
   auto put = [&](std::string_view s) {
@@ -1480,6 +1517,8 @@ int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchIm
     }
     x.route = sc.has_route ? put(sc.route) : ose_strref{0, 0};
     x.path = (sc.url_flags & OSE_URL_PATH_MASK) != OSE_URL_PATH_NONE ? put(sc.path) : ose_strref{0, 0};
+    if (sql)
+      fix_sql[q] = OtlpSqlFix{i, sc.db_flags, (sc.db_flags & OSE_DB_HAS_QUERY) ? put(sc.db_query) : ose_strref{0, 0}};
   }
   if (str_base + strs.size() + 16 > b->arena.cap) {
     // a larger arena: the message bytes move with it
@@ -1493,7 +1532,8 @@ int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchIm
   }
   c.arena_bytes = str_base + strs.size();
   const size_t fb = up(cnt * sizeof(OtlpFix)), tb = up((size_t)cnt * K + 16), vb = up((size_t)cnt * K * 8 + 16);
-  const size_t ab = up((size_t)cnt * AW * 8 + 16), fixb = fb + tb + vb + ab;
+  const size_t ab = up((size_t)cnt * AW * 8 + 16), qb = up(fix_sql.size() * sizeof(OtlpSqlFix) + 16);
+  const size_t fixb = fb + tb + vb + ab + qb;
   if ((rc = b->stage.need(fixb + strs.size() + 16))) return rc;
   DevBuf& fixdev = b->fixdev;
   if ((rc = fixdev.need(fixb))) return rc;
@@ -1503,6 +1543,7 @@ int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchIm
     std::memcpy(b->stage.p + fb + tb, fix_val.data(), (size_t)cnt * K * 8);
   }
   std::memcpy(b->stage.p + fb + tb + vb, fix_attr.data(), (size_t)cnt * AW * 8);
+  if (sql) std::memcpy(b->stage.p + fb + tb + vb + ab, fix_sql.data(), fix_sql.size() * sizeof(OtlpSqlFix));
   std::memcpy(b->stage.p + fixb, strs.data(), strs.size());
   HIP_TRY(hipMemcpyAsync(fixdev.p, b->stage.p, fixb, hipMemcpyHostToDevice, st));
   if (!strs.empty())
@@ -1531,6 +1572,11 @@ int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchIm
   fa.attr_val = a.attr_val;
   launch_otlp_fix(fa, st);
   HIP_TRY(hipGetLastError());
+  if (sql) {
+    launch_otlp_sqlop_fix(reinterpret_cast<const OtlpSqlFix*>(fixdev.p + fb + tb + vb + ab), cnt,
+                          const_cast<uint8_t*>(c.db_flags), const_cast<ose_strref*>(c.db_query), st);
+    HIP_TRY(hipGetLastError());
+  }
   HIP_TRY(hipStreamSynchronize(st));   // fixdev and the staging are reused / freed
   lap(4);
   return 0;
@@ -1541,7 +1587,7 @@ int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchIm
 namespace {
 // 0 with *host false: *o holds the outputs; 0 with *host true: the host
 // encoder takes the call (o->fallback says why); else an error code
-int encode_gpu(OtlpBatchImpl* b, const ose_outputs* outs, bool sampled, bool tmpl, const Router* router,
+int encode_gpu(OtlpBatchImpl* b, const ose_outputs* outs, bool sampled, bool tmpl, bool sql, const Router* router,
                hipStream_t st, OtlpOut* o, bool* host, std::vector<uint64_t>* res_off = nullptr) {
   *host = true;
   if (b->e->option(Engine::kOptEncodeHost)) return 0;   // engine option encode_host: the host encoder always
@@ -1573,7 +1619,8 @@ int encode_gpu(OtlpBatchImpl* b, const ose_outputs* outs, bool sampled, bool tmp
       {(void**)&a.out_total, 16 * (size_t)n_out},
       {(void**)&out_base, 8 * (size_t)n_out},
   };
-  if (tmpl) parts.push_back({(void**)&a.edit, sizeof(EncEdit) * n});
+  if (tmpl || sql) parts.push_back({(void**)&a.edit, sizeof(EncEdit) * n});
+  if (sql) parts.push_back({(void**)&a.sql_edit, sizeof(EncSqlEdit) * n});
   if (blob) parts.push_back({(void**)&routes, blob});
   // the layout arrays the decoder left on the host go up
   const bool up_scopes = !b->scopes_dev, up_res = !b->res_on_device;
@@ -1635,6 +1682,7 @@ int encode_gpu(OtlpBatchImpl* b, const ose_outputs* outs, bool sampled, bool tmp
     a.tmpl_arena = outs->tmpl_arena;
     a.tmpl_used = outs->tmpl_arena_used;
   }
+  if (sql) a.sql_op = outs->sql_op;
   a.scope_span0 = up_scopes ? scope_span0 : b->d_span0;
   a.scope_hdr = up_scopes ? scope_hdr : b->d_hdr;
   a.scope_schema = up_scopes ? scope_schema : b->d_schema;
@@ -1740,8 +1788,9 @@ int otlp_encode_gpu_offsets(Engine* e, ose_otlp_batch* bb, const ose_outputs* ou
   if (!o->work) o->work = encode_work_new();
   const bool sampled = stages & (OSE_STAGE_SAMPLE | OSE_STAGE_APPLY_KEEP);
   const bool tmpl = stages & OSE_STAGE_TEMPLATE;
+  const bool sql = stages & (OSE_STAGE_SQLOP | OSE_STAGE_APPLY_SQLOP);
   bool host = true;
-  const int rc = encode_gpu(b, outs, sampled, tmpl, router, st, o, &host, &res_off);
+  const int rc = encode_gpu(b, outs, sampled, tmpl, sql, router, st, o, &host, &res_off);
   if (rc || host) {
     otlp_out_release(o);
     return rc;
@@ -1865,6 +1914,8 @@ int ose_otlp_download(const ose_otlp_batch* bb, const ose_columns* dst) {
       {c.res_size, (void*)dst->res_size, 4 * R}, {c.scope_size, (void*)dst->scope_size, 4 * S},
       {c.scope_resource, (void*)dst->scope_resource, 4 * S}, {c.attr_type, (void*)dst->attr_type, K * n},
       {c.attr_val, (void*)dst->attr_val, 8 * K * n},
+      {c.db_flags, (void*)dst->db_flags, n}, {c.db_query, (void*)dst->db_query, 8 * n},
+      {c.res_sql_ok, (void*)dst->res_sql_ok, R},
   };
   for (auto& f : fs)
     if (f.src && f.dst && f.bytes) HIP_TRY(hipMemcpy(f.dst, f.src, f.bytes, hipMemcpyDefault));
@@ -1905,10 +1956,16 @@ int encode_threads() { return parallel_width(); }
 int ose_otlp_encode(ose_engine* eng, const ose_otlp_batch* bb, const ose_outputs* outs, uint32_t stages,
                     uint32_t group_mode, const ose_router* router, void* hip_stream, ose_otlp_out** out) {
   if (!eng || !bb || !out) return fail(OSE_EINVAL, "NULL argument");
-  // odigossqldboperationprocessor's attribute and name are not re-encoded yet
-  if (stages & (OSE_STAGE_SQLOP | OSE_STAGE_APPLY_SQLOP))
-    return fail(OSE_ENOTSUP, "ose_otlp_encode does not write odigossqldboperationprocessor's attribute and span name");
   Engine* e = reinterpret_cast<Engine*>(eng);
+  // odigossqldboperationprocessor's attribute and name are written only under
+  // the engine option otlp_sqlop (the default until the next ABI version: refused)
+  const bool sql = (stages & (OSE_STAGE_SQLOP | OSE_STAGE_APPLY_SQLOP)) != 0;
+  if (sql && !(e->has_sqlop && e->option(Engine::kOptOtlpSqlop)))
+    return fail(OSE_ENOTSUP, "ose_otlp_encode does not write odigossqldboperationprocessor's attribute and span name "
+                             "(engine option otlp_sqlop is off)");
+  if ((stages & OSE_STAGE_SQLOP) && (stages & OSE_STAGE_APPLY_SQLOP))
+    return fail(OSE_EINVAL, "OSE_STAGE_APPLY_SQLOP and OSE_STAGE_SQLOP exclude each other");
+  if (sql && (!outs || !outs->sql_op)) return fail(OSE_EINVAL, "sql_op is NULL");
   auto* b = const_cast<OtlpBatchImpl*>(reinterpret_cast<const OtlpBatchImpl*>(bb));
   if (b->e != e) return fail(OSE_EINVAL, "the batch belongs to another engine");
   if (int rc = bind_device(e)) return rc;
@@ -1937,7 +1994,7 @@ int ose_otlp_encode(ose_engine* eng, const ose_otlp_batch* bb, const ose_outputs
     }
     if (!o->work) o->work = encode_work_new();
     bool host = true;
-    const int rc = encode_gpu(b, outs, sampled, tmpl, reinterpret_cast<const Router*>(router), st, o, &host);
+    const int rc = encode_gpu(b, outs, sampled, tmpl, sql, reinterpret_cast<const Router*>(router), st, o, &host);
     if (rc || host) {
       gpu_fallback = o->fallback;
       otlp_out_release(o);   // pinned buffers taken before a failure go back to the work's pool
@@ -1949,13 +2006,14 @@ int ose_otlp_encode(ose_engine* eng, const ose_otlp_batch* bb, const ose_outputs
   }
   // the decisions and the decoder's span sizes, D2H into the batch's pinned staging
   const size_t o_keep = 0, o_url = up(n + 16), o_tmpl = o_url + up(n + 16), o_size = o_tmpl + up(8 * n + 16),
-               o_misc = o_size + up(4 * n + 16), o_arena = o_misc + 256;
+               o_misc = o_size + up(4 * n + 16), o_sql = o_misc + 256, o_arena = o_sql + up(n + 16);
   int rc;
   if ((rc = b->stage.need(o_arena))) return rc;
   uint8_t* h = b->stage.p;
   if (n) HIP_TRY(hipMemcpyAsync(h + o_size, b->cols.span_size, 4 * n, hipMemcpyDeviceToHost, st));
   if (sampled && n) HIP_TRY(hipMemcpyAsync(h + o_keep, outs->keep, n, hipMemcpyDefault, st));
   if (batch_mode) HIP_TRY(hipMemcpyAsync(h + o_misc + 8, outs->trace_keep, 1, hipMemcpyDefault, st));
+  if (sql && n) HIP_TRY(hipMemcpyAsync(h + o_sql, outs->sql_op, n, hipMemcpyDefault, st));
   if (tmpl) {
     if (n) HIP_TRY(hipMemcpyAsync(h + o_url, outs->url_out, n, hipMemcpyDefault, st));
     if (n) HIP_TRY(hipMemcpyAsync(h + o_tmpl, outs->tmpl, 8 * n, hipMemcpyDefault, st));
@@ -1974,6 +2032,7 @@ int ose_otlp_encode(ose_engine* eng, const ose_otlp_batch* bb, const ose_outputs
       if (n) HIP_TRY(hipMemcpyAsync(h + o_url, outs->url_out, n, hipMemcpyDefault, st));
       if (n) HIP_TRY(hipMemcpyAsync(h + o_tmpl, outs->tmpl, 8 * n, hipMemcpyDefault, st));
       if (batch_mode) HIP_TRY(hipMemcpyAsync(h + o_misc + 8, outs->trace_keep, 1, hipMemcpyDefault, st));
+      if (sql && n) HIP_TRY(hipMemcpyAsync(h + o_sql, outs->sql_op, n, hipMemcpyDefault, st));
       HIP_TRY(hipMemcpyAsync(h + o_arena, outs->tmpl_arena, used, hipMemcpyDefault, st));
       HIP_TRY(hipStreamSynchronize(st));
     }
@@ -1988,6 +2047,7 @@ int ose_otlp_encode(ose_engine* eng, const ose_otlp_batch* bb, const ose_outputs
     d.tmpl_arena_len = used;
   }
   d.span_size = reinterpret_cast<const uint32_t*>(h + o_size);
+  if (sql) d.sql_op = h + o_sql;
   if ((rc = layout_to_host(b, st))) return rc;
   auto* o = new OtlpOut();
   o->e = e;
@@ -2014,10 +2074,11 @@ int ose_otlp_encode(ose_engine* eng, const ose_otlp_batch* bb, const ose_outputs
 
 // Test seam (CPU): the encoder on the host walk of `pb` with the given
 // decisions (keep / url_out / tmpl NULL when absent) and span sizes
-// computed on the host as the decoder would.
-int osehost_otlp_encode(const uint8_t* pb, size_t len, const uint8_t* keep, int drop_all, const uint8_t* url_out,
-                        const ose_strref* tmpl, const uint8_t* tmpl_arena, uint64_t tmpl_arena_len,
-                        const ose_router* router, int threads, ose_otlp_out** out) {
+// computed on the host as the decoder would.  sql_op: OSE_SQLOP_* per span
+// (odigossqldboperationprocessor's decisions), NULL when absent.
+int osehost_otlp_encode_sql(const uint8_t* pb, size_t len, const uint8_t* keep, int drop_all, const uint8_t* url_out,
+                            const ose_strref* tmpl, const uint8_t* tmpl_arena, uint64_t tmpl_arena_len,
+                            const ose_router* router, int threads, ose_otlp_out** out, const uint8_t* sql_op) {
   if ((!pb && len) || !out) return fail(OSE_EINVAL, "NULL argument");
   ColumnizeCtx ctx;
   std::string err = ctx.build(nullptr, nullptr, nullptr);
@@ -2041,6 +2102,7 @@ int osehost_otlp_encode(const uint8_t* pb, size_t len, const uint8_t* keep, int 
   d.tmpl_arena = tmpl_arena;
   d.tmpl_arena_len = tmpl_arena_len;
   d.span_size = sizes.data();
+  d.sql_op = sql_op;
   auto* o = new OtlpOut();
   o->work = encode_work_new();
   if (!encode_traces(pb, len, w.span_ref, w.lay, d, reinterpret_cast<const Router*>(router),
@@ -2050,6 +2112,13 @@ int osehost_otlp_encode(const uint8_t* pb, size_t len, const uint8_t* keep, int 
   }
   *out = reinterpret_cast<ose_otlp_out*>(o);
   return 0;
+}
+
+int osehost_otlp_encode(const uint8_t* pb, size_t len, const uint8_t* keep, int drop_all, const uint8_t* url_out,
+                        const ose_strref* tmpl, const uint8_t* tmpl_arena, uint64_t tmpl_arena_len,
+                        const ose_router* router, int threads, ose_otlp_out** out) {
+  return osehost_otlp_encode_sql(pb, len, keep, drop_all, url_out, tmpl, tmpl_arena, tmpl_arena_len, router, threads, out,
+                                 nullptr);
 }
 
 void ose_otlp_release(ose_otlp_batch* bb) {

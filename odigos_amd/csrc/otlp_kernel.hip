@@ -658,7 +658,8 @@ __global__ __launch_bounds__(kOThreads) void otlp_res_fields_kernel(OtlpResArgs 
       a.res_svc[r] = e.svc;
       a.res_svc_str[r] = e.svc_str;
       a.res_set[r] = e.set;
-      a.res_ok[r] = (uint8_t)e.ok;
+      a.res_ok[r] = (uint8_t)(e.ok & 1u);
+      if (a.res_sql_ok) a.res_sql_ok[r] = (uint8_t)((e.ok >> 1) & 1u);
       a.attr_res[r] = e.attr_res;
       a.res_size[r] = e.rpart + (schema ? (uint32_t)field_len(schema) : 0u);
       found = true;
@@ -705,7 +706,8 @@ __global__ __launch_bounds__(kOThreads) void otlp_res_fix_kernel(OtlpResArgs a, 
   a.res_svc[x.row] = x.svc;
   a.res_svc_str[x.row] = x.svc_str;
   a.res_set[x.row] = x.set;
-  a.res_ok[x.row] = (uint8_t)x.ok;
+  a.res_ok[x.row] = (uint8_t)(x.ok & 1u);
+  if (a.res_sql_ok) a.res_sql_ok[x.row] = (uint8_t)((x.ok >> 1) & 1u);
   a.attr_res[x.row] = x.attr_res;
   a.res_size[x.row] = x.rpart + (sch ? (uint32_t)field_len(sch) : 0u);
 }

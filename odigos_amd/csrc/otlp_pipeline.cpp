@@ -135,7 +135,7 @@ struct Req {
 struct Slot {
   hipStream_t st = nullptr;
   uint8_t* msg = nullptr;   // pinned, max_bytes
-  DBuf keep, url, tmpl, arena, sets, misc;   // the stages' device outputs
+  DBuf keep, url, tmpl, arena, sets, misc, sql;   // the stages' device outputs (sql: sql_op, with OSE_STAGE_SQLOP)
   uint64_t* host_misc = nullptr;              // pinned: status, accepted, the attribute-set counters
   size_t host_misc_cap = 0;
   enum State { Idle, Filling, Running } state = Idle;
@@ -208,6 +208,7 @@ int run_front(Pipeline* p, Slot& s, const uint8_t* pb, size_t len, const ose_ran
   if ((rc = s.keep.need(n)) || (rc = s.url.need(n)) || (rc = s.tmpl.need(8 * n)) || (rc = s.arena.need(tcap)) ||
       (rc = s.sets.need(8 * sets)) || (rc = s.misc.need(64)))
     return rc;
+  if ((p->stages & OSE_STAGE_SQLOP) && (rc = s.sql.need(n))) return rc;
   outs = ose_outputs{};
   outs.keep = s.keep.p;
   outs.url_out = s.url.p;
@@ -218,6 +219,7 @@ int run_front(Pipeline* p, Slot& s, const uint8_t* pb, size_t len, const ose_ran
   outs.accepted_spans = reinterpret_cast<int64_t*>(s.misc.p + 8);
   outs.device_status = reinterpret_cast<uint32_t*>(s.misc.p + 16);
   outs.attrset_bytes = reinterpret_cast<int64_t*>(s.sets.p);
+  if (p->stages & OSE_STAGE_SQLOP) outs.sql_op = s.sql.p;
   PIPE_TRY(hipMemsetAsync(s.misc.p, 0, 64, s.st));
   PIPE_TRY(hipMemsetAsync(s.sets.p, 0, 8 * sets, s.st));
   return ose_process_device(eng, c, &outs, p->stages, OSE_GROUP_TRACE_ID, &rnd, s.st);
@@ -486,12 +488,15 @@ int ose_otlp_pipeline_create(ose_engine* eng, const ose_router* router, uint32_t
                              ose_otlp_pipeline** out) {
   if (!eng || !out) return fail(OSE_EINVAL, "NULL argument");
   *out = nullptr;
-  if (stages & (OSE_STAGE_SQLOP | OSE_STAGE_APPLY_SQLOP))
-    return fail(OSE_ENOTSUP, "the OTLP path does not carry odigossqldboperationprocessor (db.query.text is not decoded, "
-                             "the attribute and name are not re-encoded)");
-  if (stages & ~(OSE_STAGE_SAMPLE | OSE_STAGE_TEMPLATE | OSE_STAGE_SIZE))
-    return fail(OSE_EINVAL, "the pipeline runs SAMPLE, TEMPLATE and SIZE only");
   Engine* e = reinterpret_cast<Engine*>(eng);
+  // odigossqldboperationprocessor rides the OTLP path only under the engine
+  // option otlp_sqlop, as set when the pipeline is created
+  const bool sql_on = e->has_sqlop && e->option(Engine::kOptOtlpSqlop);
+  if (!sql_on && (stages & (OSE_STAGE_SQLOP | OSE_STAGE_APPLY_SQLOP)))
+    return fail(OSE_ENOTSUP, "the OTLP path does not carry odigossqldboperationprocessor (db.query.text is not decoded, "
+                             "the attribute and name are not re-encoded) unless the engine option otlp_sqlop is on");
+  if (stages & ~(OSE_STAGE_SAMPLE | OSE_STAGE_TEMPLATE | OSE_STAGE_SIZE | OSE_STAGE_SQLOP))
+    return fail(OSE_EINVAL, "the pipeline runs SAMPLE, TEMPLATE, SQLOP and SIZE only");
   if (int rc = bind_device(e)) return rc;
   auto* p = new Pipeline();
   p->e = e;

@@ -220,6 +220,9 @@ def lib() -> C.CDLL:
         "osehost_otlp_walk": (_p, [C.c_char_p, C.c_char_p, C.c_size_t]),
         "osehost_otlp_encode": (C.c_int, [C.c_char_p, C.c_size_t, _p, C.c_int, _p, _p, _p, C.c_uint64, _p, C.c_int,
                                           C.POINTER(_p)]),
+        # ... plus sql_op (odigossqldboperationprocessor's decisions, NULL when absent)
+        "osehost_otlp_encode_sql": (C.c_int, [C.c_char_p, C.c_size_t, _p, C.c_int, _p, _p, _p, C.c_uint64, _p, C.c_int,
+                                              C.POINTER(_p), _p]),
         "osehost_router_create_signal": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(_p)]),
         "osehost_router_route": (_p, [_p, C.c_char_p]),
         "osehost_otlp_out_timings": (C.c_int, [_p, C.POINTER(C.c_double)]),

@@ -11,6 +11,12 @@ output side (ose_otlp_encode: decisions D2H, routing to data-stream
 pipelines, one TracesData per pipeline).
 The span decoder's roofline: message bytes read + columns written per
 launch over its HIP-event time, against 8 TB/s.
+
+--sqlop: the query-operation-detector profile on the same path: the engine
+has the odigossqldboperationprocessor section and the engine option
+otlp_sqlop on, the stages include SQLOP, and a third of the spans carry a
+db.query.text (as in tools/sqlop_bench.py).  The decoder's second pass
+(otlp_sqlop_kernel) is reported as a row of its own, with its roofline.
 """
 from __future__ import annotations
 
@@ -28,8 +34,12 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--spans", type=int, default=10_000_000)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--sqlop", action="store_true", help="odigossqldboperationprocessor through the OTLP path")
     ap.add_argument("--out", default=str(ROOT / "gpurun_out" / "otlp.json"))
     args = ap.parse_args()
+    if args.sqlop and args.out == ap.get_default("out"):   # a file of its own beside the default
+        args.out = str(Path(args.out).with_name("otlp_sqlop.json"))
+    sql_every = 3 if args.sqlop else 0
     import torch
     from bench import NODE_KEYS, cpu_share
     from odigos_amd import native
@@ -39,13 +49,18 @@ def main():
     threads = max(1, min(16, share))
     t = time.perf_counter()
     g = Generator("fused", seed=0x0D16F0A1, n_spans=args.spans, threads=threads)
-    pb = g.otlp(threads)
+    pb = g.otlp(threads, sql_every)
     print(f"generated {len(pb) / 1e9:.2f} GB for {args.spans} spans in {time.perf_counter() - t:.1f}s", flush=True)
     cfg = {"odigossampling": c3_sampling_config(), "odigosurltemplate": {},
            "odigostrafficmetrics": {"res_attributes_keys": NODE_KEYS}}
+    if args.sqlop:
+        cfg["odigossqldboperationprocessor"] = {}
     eng = Engine(cfg)
     pin = PinnedBuffer(pb)
     st = native.STAGE_SAMPLE | native.STAGE_TEMPLATE | native.STAGE_SIZE
+    if args.sqlop:
+        eng.set_option("otlp_sqlop", 1)
+        st |= native.STAGE_SQLOP
     sh = torch.cuda.current_stream().cuda_stream
 
     # outputs allocated once (the shim keeps its buffers); template arena 64 B/span
@@ -79,14 +94,16 @@ def main():
         c = time.perf_counter()
         if stages:
             out = ob.encode(st, native.GROUP_TRACE_ID, router, stream=sh, copy=False)
-            enc.append((time.perf_counter() - c, out, ob.encode_ms))
+            enc.append((time.perf_counter() - c, out, ob.encode_ms, ob.encode_path))
         info = (ob.cols.n_spans, ob.host_spans, int(ob.out_numpy("device_status", n=1)[0]) if stages else 0)
         ob.close()
         return b - a, c - b, info
 
     for _ in range(2):
         one(True, True)
-    res = {"metric": "OTLP protobuf ingest: host TracesData bytes -> decoded columns -> SAMPLE|TEMPLATE|SIZE",
+    res = {"metric": "OTLP protobuf ingest: host TracesData bytes -> decoded columns -> SAMPLE|TEMPLATE|" +
+                     ("SQLOP|SIZE" if args.sqlop else "SIZE"),
+           "sqlop": bool(args.sqlop),
            "spans": args.spans, "message_bytes": len(pb), "bytes_per_span": len(pb) / args.spans,
            "host_cpu": model, "cpu_share": share, "nproc": nproc}
     eng.profile(True)
@@ -100,7 +117,8 @@ def main():
     eng.profile(False)
     n_dec = prof.get("otlp_span_kernel", {"ms": 0.0, "launches": 1})
     k_ms = n_dec["ms"] / max(n_dec["launches"], 1)
-    stage_ms = sum(v["ms"] for k, v in prof.items() if k != "otlp_span_kernel") / args.reps
+    decode_kernels = ("otlp_span_kernel", "otlp_sqlop_kernel")
+    stage_ms = sum(v["ms"] for k, v in prof.items() if k not in decode_kernels) / args.reps
     dp = min(dec)
     res["decode_pinned_ms"] = dp * 1e3
     best = phases[2 + dec.index(dp)]
@@ -111,8 +129,19 @@ def main():
     res["decode_spans_per_s"] = args.spans / dp
     res["host_pass_spans"] = info[1]
     res["span_kernel_ms"] = k_ms
+    if args.sqlop:
+        # the second pass: the span payloads again (the message bytes), span_ref and the
+        # span kernel's host flag read, db_flags + db_query written
+        q = prof.get("otlp_sqlop_kernel", {"ms": 0.0, "launches": 1})
+        q_ms = q["ms"] / max(q["launches"], 1)
+        q_alg = len(pb) + (8 + 1) * args.spans + (1 + 8) * args.spans
+        res["sqlop_decode_kernel_ms"] = q_ms
+        res["sqlop_decode_kernel_roofline"] = {"bound": "hbm", "achieved": q_alg / (q_ms * 1e-3) / 1e9 if q_ms else 0.0,
+                                               "peak": 8000.0, "unit": "GB/s", "algorithmic_bytes": q_alg}
+        res["sqlop_decode_kernel_roofline"]["frac"] = res["sqlop_decode_kernel_roofline"]["achieved"] / 8000.0
     e_best = min(enc[2:], key=lambda x: x[0])
     res["encode_ms"] = e_best[0] * 1e3
+    res["encode_path"] = e_best[3]
     res["encode_phases_ms"] = dict(zip(("decisions_d2h", "sizing", "buffers", "writing"), e_best[2]))
     res["encode_outputs"] = [{"pipeline": p, "bytes": nb, "resources": nr} for p, nb, nr in e_best[1]]
     out_bytes = sum(x["bytes"] for x in res["encode_outputs"])
@@ -126,7 +155,7 @@ def main():
     d, _, _ = one(False, False)
     res["decode_pageable_ms"] = d * 1e3
     # per-call latency at the batch processor's 8192 spans
-    smallpb = Generator("fused", seed=0x0D16F0A2, n_spans=8192, threads=threads).otlp(threads)
+    smallpb = Generator("fused", seed=0x0D16F0A2, n_spans=8192, threads=threads).otlp(threads, sql_every)
     spin = PinnedBuffer(smallpb)
     sdims = native.Columns()
     sdims.n_spans, sdims.n_resources, sdims.n_attrsets = 8192, 8192, 4096
