@@ -383,8 +383,13 @@ uint32_t ose_engine_attr_host_rules(const ose_engine* eng, uint64_t* words, uint
  * batch repeated a trace id (the run-list path ran), counts[1] = calls some
  * trace of which overflowed the run lists and was decided by the radix sort
  * by trace id, counts[2] = long-run passes (traces still open 4 steps past
- * their first window).  Synchronises the engine's device.  Writes
- * min(cap, 3) counters and returns 3.                                      */
+ * their first window).  With the engine option "url_path_counts" on,
+ * counts[3] = the 64-span groups url_plan_slow_kernel planned in the engine's
+ * most recent TEMPLATE call (groups url_plan_kernel could not stage or list)
+ * and counts[4] = the groups url_emit_slow_kernel emitted in that call
+ * (groups not assembled in LDS); both stay 0 while the option is off.
+ * Synchronises the engine's device.  Writes min(cap, 5) counters and
+ * returns 5.                                                                */
 uint32_t ose_engine_path_counts(ose_engine* eng, uint64_t* counts, uint32_t cap);
 
 /* Attribute key k (< n_attr_keys) of the attr_type / attr_val columns; the
@@ -409,6 +414,11 @@ int ose_engine_attr_key(const ose_engine* eng, uint32_t k, const char** key, uin
  *                          without the odigossqldboperationprocessor section.
  *                          Off by default; on by default from the next ABI
  *                          version.
+ * and one witness for tests:
+ *   "url_path_counts"      every TEMPLATE call queues two 4-byte device copies
+ *                          behind url_emit_slow_kernel, which keep the call's
+ *                          list lengths for ose_engine_path_counts (counts[3],
+ *                          counts[4]).  Off by default: nothing extra is queued.
  * OSE_EINVAL for any other name.                                            */
 int ose_engine_set_option(ose_engine* eng, const char* name, int64_t value);
 

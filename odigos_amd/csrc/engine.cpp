@@ -472,6 +472,12 @@ int run_url(Engine* e, const ose_columns* c, const ose_outputs* o, hipStream_t s
   launch_url_emit_slow(a, st);
   HIP_TRY(hipGetLastError());
   e->prof_end(tm, st);
+  // "url_path_counts" (tests): which kernel took this call's groups, kept in
+  // two spare words of the engine's path counters (ose_engine_path_counts)
+  if ((e->options.load() & Engine::kOptUrlPathCounts) && e->path_count_dev) {
+    HIP_TRY(hipMemcpyAsync(e->path_count_dev + 2, a.unplanned_count, 4, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(e->path_count_dev + 3, a.slow_count, 4, hipMemcpyDeviceToDevice, st));
+  }
   if (front) {
     *front = a;
     return 0;
@@ -871,17 +877,21 @@ int ose_engine_create(const char* cfg_json, ose_engine** out) {
 uint32_t ose_engine_path_counts(ose_engine* eng, uint64_t* counts, uint32_t cap) {
   if (!eng) return 0;
   Engine* e = reinterpret_cast<Engine*>(eng);
-  uint64_t c[3] = {0, 0, e->long_run_passes.load()};
+  uint64_t c[5] = {0, 0, 0, 0, 0};
   if (e->path_count_dev && bind_device(e) == 0) {
     LastErrorScope keep("ose_engine_path_counts");
     // counters the queued work has not reached yet are not counted: the
     // device is synchronised first
     if (hipDeviceSynchronize() != hipSuccess ||
-        hipMemcpy(c, e->path_count_dev, 16, hipMemcpyDeviceToHost) != hipSuccess)
-      c[0] = c[1] = 0;
+        hipMemcpy(c, e->path_count_dev, 32, hipMemcpyDeviceToHost) != hipSuccess)
+      c[0] = c[1] = c[2] = c[3] = 0;
   }
-  for (uint32_t k = 0; k < 3 && k < cap && counts; k++) counts[k] = c[k];
-  return 3;
+  // device words 2 and 3 (the URL stage's lists, "url_path_counts") are counts[3] and [4]
+  c[4] = c[3];
+  c[3] = c[2];
+  c[2] = e->long_run_passes.load();
+  for (uint32_t k = 0; k < 5 && k < cap && counts; k++) counts[k] = c[k];
+  return 5;
 }
 
 void ose_engine_destroy(ose_engine* eng) {
@@ -949,6 +959,7 @@ int ose_engine_set_option(ose_engine* eng, const char* name, int64_t value) {
       {"otlp_host_scopes", Engine::kOptOtlpHostScopes},
       {"encode_host", Engine::kOptEncodeHost},
       {"otlp_sqlop", Engine::kOptOtlpSqlop},
+      {"url_path_counts", Engine::kOptUrlPathCounts},
   };
   for (const auto& o : kOpts) {
     if (strcmp(name, o.name) != 0) continue;

@@ -123,7 +123,8 @@ struct Engine {
   // kOptOtlpSqlop is a feature switch, not an alternative leg: the OTLP
   // path carries odigossqldboperationprocessor (off until the next ABI version)
   enum : uint32_t {
-    kOptOtlpGpuChain = 1, kOptOtlpHostResources = 2, kOptOtlpHostScopes = 4, kOptEncodeHost = 8, kOptOtlpSqlop = 16
+    kOptOtlpGpuChain = 1, kOptOtlpHostResources = 2, kOptOtlpHostScopes = 4, kOptEncodeHost = 8, kOptOtlpSqlop = 16,
+    kOptUrlPathCounts = 32   // run_url keeps the call's unplanned / slow list lengths (ose_engine_path_counts)
   };
   std::atomic<uint32_t> options{0};
   bool option(uint32_t o) const { return (options.load(std::memory_order_relaxed) & o) != 0; }
@@ -147,7 +148,9 @@ struct Engine {
   std::vector<uint32_t> sampling_lat_svc;
   uint8_t* shard_tables_dev = nullptr;
   // which slow paths the trace stage took (ose_engine_path_counts): [0] run
-  // lists, [1] the radix sort (device counters), [2] long-run passes (host)
+  // lists, [1] the radix sort (device counters), [2] long-run passes (host);
+  // device words [2] and [3]: the URL stage's unplanned and slow list lengths
+  // of the most recent TEMPLATE call ("url_path_counts")
   unsigned long long* path_count_dev = nullptr;
   std::atomic<uint64_t> long_run_passes{0};
   std::unordered_map<std::string, uint32_t> service_ids;
