@@ -58,7 +58,7 @@ struct UrlCfgDev {
 namespace ose {
 
 // odigossampling tables (sampling_host.cpp builds them from the decoded
-// Config; trace_kernel.hip reads them).  Rules are stored in level order
+// Config; the trace files read them through trace_device.hpp load_cfg).  Rules are stored in level order
 // global, service, endpoint (rule_engine.go:56-60), config order inside a
 // level (evaluateLevel is an order-sensitive fold, rule_engine.go:89-115).
 enum : uint32_t { kSampError = 0, kSampLatency = 1, kSampService = 2 };

@@ -44,6 +44,9 @@ __device__ __forceinline__ uint32_t wave_incl_sum_u32(uint32_t x) {
   return x;
 }
 __device__ __forceinline__ uint32_t lane_value(uint32_t x, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)x, l); }
+__device__ __forceinline__ uint64_t lane_value64(uint64_t x, int l) {
+  return (uint64_t)lane_value((uint32_t)x, l) | ((uint64_t)lane_value((uint32_t)(x >> 32), l) << 32);
+}
 // wave-uniform min / max (lanes 15, 31, 47, 63 hold their row's after the row_shr steps)
 __device__ __forceinline__ uint32_t wave_min_u32(uint32_t x) {
   x = min(x, dpp_mov<0x111>(x, x));

@@ -59,7 +59,7 @@ struct Workspace {
   bool pending_set = false;
   bool captured = false;          // taken by a hipGraph capture: never returned to the pool
   int reserve(size_t bytes);
-  // exact trace_id hash table of the SAMPLE stage (trace_kernel.hip), kept
+  // exact trace_id hash table of the SAMPLE stage (trace_slow_kernel.hip table_insert), kept
   // across calls: entries carry a generation tag, so nothing is cleared
   void* table = nullptr;
   uint64_t table_slots_cap = 0;

@@ -32,8 +32,7 @@
 #include <algorithm>
 #include <cstdint>
 
-#include "device_common.hpp"
-#include "kernels.hpp"
+#include "trace_device.hpp"   // tid_hash: the trace table's hash
 
 namespace ose {
 
@@ -62,13 +61,6 @@ __device__ __forceinline__ bool gbt_evicted(const GbtArgs& a, uint64_t seq) {
   return a.wcnt[t >> 40] > (t & ((1ull << 40) - 1)) + a.worker_cap;
 }
 
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-
 // The id table persists across adds.  A slot holds an id and the creation
 // number of its newest trace; the trace is live for an added span iff that
 // number is in [live_lo, live_hi) (not released, evicted or expired).  A
@@ -78,7 +70,7 @@ __device__ __forceinline__ uint64_t mix64(uint64_t x) {
 // the table grows or tombstones fill half of it, so an add costs O(batch),
 // not O(traces waiting).
 //
-// Slots are published with the trace table's protocol (trace_kernel.hip): a
+// Slots are published with the trace table's protocol (trace_slow_kernel.hip table_insert): a
 // stale-epoch slot is claimed BUSY, its fields stored with agent-scope
 // stores, drained, then READY.
 
@@ -86,7 +78,7 @@ __device__ __forceinline__ uint64_t mix64(uint64_t x) {
 // [live_lo, live_hi), so each id occurs at most once; the newest wins anyway)
 __device__ void gbt_put(const GbtArgs& a, uint64_t hi, uint64_t lo, uint64_t seq) {
   const uint32_t busy = (a.epoch << 2) | 1u, ready = (a.epoch << 2) | 2u;
-  uint64_t h = mix64(hi ^ mix64(lo)) & a.table_mask;
+  uint64_t h = tid_hash(hi, lo) & a.table_mask;
   uint32_t probes = 0, spins = 0;
   for (;;) {
     GbtSlot* s = &a.table[h];
@@ -132,7 +124,7 @@ __device__ void gbt_put(const GbtArgs& a, uint64_t hi, uint64_t lo, uint64_t seq
 __device__ uint64_t gbt_lookup(const GbtArgs& a, uint64_t hi, uint64_t lo, uint32_t pos) {
   const uint32_t busy = (a.epoch << 2) | 1u, ready = (a.epoch << 2) | 2u;
   const uint64_t mine = kGbtUnset | a.add_gen;
-  uint64_t h = mix64(hi ^ mix64(lo)) & a.table_mask;
+  uint64_t h = tid_hash(hi, lo) & a.table_mask;
   uint32_t probes = 0, spins = 0;
   for (;;) {
     GbtSlot* s = &a.table[h];

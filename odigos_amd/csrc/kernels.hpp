@@ -169,7 +169,7 @@ void launch_url_emit_slow(const UrlKernelArgs& a, hipStream_t st);
 namespace ose {
 
 // odigossampling: trace grouping, per-trace reduction and the rule fold
-// (trace_kernel.hip).  A "position" is an index into the evaluation order:
+// (trace_kernel.hip; the slow paths: trace_slow_kernel.hip).  A "position" is an index into the evaluation order:
 // the batch order itself (fast path) or the stable sort of spans by trace
 // (slow path, perm != null).
 struct TraceSlot {            // exact trace_id hash table entry (32 B)
@@ -293,12 +293,13 @@ constexpr uint32_t kMultiCfgLds = 24576;
 constexpr uint32_t kDupBucketCap = 1024;   // fingerprints per bucket (more: the exact path decides)
 void launch_trace_dup_check(const TraceKernelArgs& a, hipStream_t st);
 void launch_trace_long(const TraceKernelArgs& a, hipStream_t st, uint32_t known_runs = 0);
+// trace_slow_kernel.hip: the run-list path and the sort path
 void launch_trace_insert_exact(const TraceKernelArgs& a, hipStream_t st);   // slow path, gated on *dup
 void launch_trace_runs(const TraceKernelArgs& a, hipStream_t st);           // run-list path (gated on *dup)
 void launch_trace_fold(const TraceKernelArgs& a, hipStream_t st);
 void launch_trace_first_select(const TraceKernelArgs& a, hipStream_t st);   // win_first -> win_heads unless *overflow
 
-// Slow path (runs only when *dup != 0; every launch checks the flag first).
+// Sort path (trace_slow_kernel.hip; runs only when *gate != 0: every launch checks the flag first).
 struct TraceSortArgs {
   uint64_t n_spans;
   uint32_t n_tiles;           // ceil(n / kSortTile)
@@ -344,7 +345,7 @@ struct ScanArgs {
 constexpr uint32_t kScanTileItems = 1024;
 void launch_scan_u32(const ScanArgs& a, hipStream_t st);
 
-// Dense per-trace outputs from the records (first-appearance order).
+// Dense per-trace outputs from the records (first-appearance order; trace_slow_kernel.hip).
 struct TraceCompactArgs {
   uint32_t n_windows;
   const uint64_t* win_heads;
@@ -357,7 +358,7 @@ struct TraceCompactArgs {
 };
 void launch_trace_compact(const TraceCompactArgs& a, hipStream_t st);
 
-// Trace-id exchange (ose_shard_*; trace_kernel.hip).
+// Trace-id exchange (ose_shard_*; shard_kernel.hip).
 struct ShardArgs {
   uint64_t n_spans;
   uint32_t n_tiles;           // wave chunks: ceil(n / kXChunk)
@@ -390,7 +391,7 @@ struct ShardArgs {
   uint8_t* send;              // [records * x_rec_bytes(n_chunks)], records <= n
   uint32_t* pack_pos;         // [n] slot of each span's record
 };
-// Partial record (trace_kernel.hip "trace-id exchange"): u64 words hi, lo,
+// Partial record (shard_kernel.hip "trace-id exchange"): u64 words hi, lo,
 // min start, max end, {latency service 24 | flags 8}, then per rule chunk
 // the endpoint bits and the rule bits of that chunk's tables.
 constexpr uint32_t kXSteps = 16;                        // 64-span steps of one packing wave's chunk
@@ -418,7 +419,7 @@ struct UnpackArgs {
 };
 void launch_shard_unpack(const UnpackArgs& a, hipStream_t st);
 // Owner-side decisions straight from the received records (ose_shard_decide;
-// trace_kernel.hip "owner side"): records bucketed by trace-id hash, one
+// shard_kernel.hip "owner side"): records bucketed by trace-id hash, one
 // workgroup per bucket groups, orders and folds its traces in LDS.
 constexpr uint32_t kOwnerCap = 256;   // records one bucket holds (a fuller bucket: the general path)
 constexpr uint32_t kOwnerAvg = 80;    // records per bucket the host sizes the bucket count for
@@ -443,14 +444,15 @@ struct OwnerArgs {
 void launch_owner_bucket(const OwnerArgs& a, hipStream_t st);
 void launch_owner_fold(const OwnerArgs& a, hipStream_t st);
 void launch_scatter_keep(const uint8_t* back, const uint32_t* pos, uint64_t n, uint8_t* keep, hipStream_t st);
-// endpoint bits of every span under one rule chunk's tables in HBM (a chunk
-// whose route bytes spill past the LDS copy): out[j] for span j
+// trace_kernel.hip, per rule chunk:
 // out[r] = map[in[r]] (0xFFFFFFFF for ids >= n_global), for res_svc and res_svc_str
 void launch_svc_translate(const uint32_t* map, uint32_t n_global, const uint32_t* in1, const uint32_t* in2, uint32_t* out1,
                           uint32_t* out2, uint64_t n, hipStream_t st);
+// endpoint bits of every span under one rule chunk's tables in HBM (a chunk
+// whose route bytes spill past the LDS copy): out[j] for span j
 void launch_endpoint_plane(const uint8_t* cfg, const uint32_t* resource, const uint32_t* res_svc, const ose_strref* route,
                            const uint8_t* arena, uint64_t n, uint64_t* out, hipStream_t st);
-// the in-process transport's pieces of one phase, moved by one launch
+// the in-process transport's pieces of one phase, moved by one launch (shard_kernel.hip)
 struct PeerCopies {
   const uint8_t* src[64];
   uint8_t* dst[64];

@@ -1,5 +1,5 @@
 // sampling_host.cpp — odigossampling: rule tables (built once per engine)
-// and the launch sequence of the trace stage (trace_kernel.hip).
+// and the launch sequence of the trace stage (trace_kernel.hip, trace_slow_kernel.hip).
 #include <algorithm>
 #include <map>
 #include <string>
@@ -174,7 +174,7 @@ int build_sampling_blob(const std::unordered_map<std::string, uint32_t>& service
 // (a rule whose route alone does not fit: a chunk of its own whose route
 // bytes past kSampCfgLds the kernels read from HBM);
 // the trace stage then runs once per chunk and carries ShouldSample's walk
-// from one to the next (trace_kernel.hip decide_chunk), so every config
+// from one to the next (trace_device.hpp decide_chunk), so every config
 // Validate accepts runs (the span_attribute bits of a span stay one 64-bit
 // attr_match word: at most 64 span_attribute rules, as columnize.cpp).
 int Engine::build_sampling_tables() {

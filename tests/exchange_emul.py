@@ -1,7 +1,7 @@
 """numpy restatement of the trace-id exchange (test infrastructure): owner
 hash, the partial records and their stable per-owner bucketing, the owner-side
 columns ose_shard_unpack writes, and an expansion of records into plain
-spans for the oracle (odigos_amd/csrc/trace_kernel.hip shard_* kernels,
+spans for the oracle (odigos_amd/csrc/shard_kernel.hip shard_* kernels,
 include/odigos_amd.h "trace-id exchange"), plus CPU ops for
 odigos_amd.exchange.route_and_sample.
 

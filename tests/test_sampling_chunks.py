@@ -2,7 +2,7 @@
 rules, more than 64 distinct service_name services, tables beyond the LDS
 budget.  The engine cuts the level-ordered rule list into chunks and runs the
 trace stage once per chunk, carrying ShouldSample's walk per trace
-(sampling_host.cpp build_sampling_tables / run_sampling, trace_kernel.hip
+(sampling_host.cpp build_sampling_tables / run_sampling, trace_device.hpp
 decide_chunk).  The reference accepts these configs (odigossamplingprocessor
 config.go:17-80 Validate has no rule-count bound; rule_engine.go:55-115
 folds any number of rules).
