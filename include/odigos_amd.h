@@ -270,8 +270,10 @@ typedef struct ose_columns {
    * true for the resource; NULL = every resource passes.  ose_otlp_decode
    * fills them under the engine option "otlp_sqlop" only (db_query then
    * points into the message bytes, or at the host pass's AsString text after
-   * them; else the columns of ose_otlp_columns are NULL); ose_gbt_add does not
-   * carry them (the columns of ose_gbt_release have them NULL).             */
+   * them; else the columns of ose_otlp_columns are NULL); ose_gbt_add stores
+   * them and ose_gbt_release returns them when the store's engine has the
+   * odigossqldboperationprocessor section (else it ignores them and the
+   * released columns have them NULL).                                      */
   const uint8_t* db_flags;
   const ose_strref* db_query;
   const uint8_t* res_sql_ok;
@@ -682,7 +684,8 @@ void ose_otlp_pipeline_destroy(ose_otlp_pipeline* p);
  * `sampling_controller.go:193-220`).  cfg_json: {"wait_duration": "30s",
  * "num_traces": 1000000, "num_workers": 1} (the processor's keys; Go
  * durations).  Spans wait on the GPU (span_capacity spans, arena_capacity
- * bytes of their route / path / attribute strings) until wait_duration after
+ * bytes of their route / path / attribute strings and, on an engine with the
+ * odigossqldboperationprocessor section, their db_query bytes) until wait_duration after
  * their trace's first span; ose_gbt_release then returns every trace whose
  * time has come as one device batch: each trace contiguous, its pieces (one
  * per ResourceSpans x ScopeSpans it arrived in) in arrival order as
@@ -695,7 +698,15 @@ void ose_otlp_pipeline_destroy(ose_otlp_pipeline* p);
  * contrib's event machine shards traces; num_traces >= W, else OSE_EINVAL).
  * now_ns is the caller's clock and must not go backwards.
  * attrset_map (n_attrsets of the added batch, may be NULL = identity) maps
- * the batch's res_attrset ids to ids stable across batches.  The released
+ * the batch's res_attrset ids to ids stable across batches.  On an engine
+ * with the odigossqldboperationprocessor section the store also carries the
+ * three SQL columns: db_flags (NULL = 0 for every span), db_query (read only
+ * under OSE_DB_HAS_QUERY; NULL beside a non-NULL db_flags is OSE_EINVAL; as
+ * for route and path, off + len <= arena_bytes is the caller's word) and
+ * res_sql_ok (NULL = 1 for every resource).  The query bytes count toward
+ * arena_capacity and the string bytes held.  The release returns the three
+ * columns (res_sql_ok per released resource), its arena 16-byte aligned with
+ * 16 readable bytes after arena_bytes, as OSE_STAGE_SQLOP needs.  The released
  * columns stay valid until the next release; OSE_ERANGE when the store is
  * full (more spans than the capacity within one wait_duration).            */
 typedef struct ose_gbt ose_gbt;

@@ -377,7 +377,16 @@ class Router:
 class GroupByTrace:
     """The GPU-resident groupbytrace store (ose_gbt_*): add device batches
     with the caller's clock, release the traces whose wait is over as one
-    device batch (DeviceView) for Engine.process_device."""
+    device batch (DeviceView) for Engine.process_device.
+
+    On an engine with the odigossqldboperationprocessor section the store
+    also carries db_flags, db_query (the query bytes wait in the arena ring
+    with the span's other strings and count toward arena_capacity and
+    held_bytes) and res_sql_ok: add() takes them from the batch (db_flags
+    None = 0 for every span, res_sql_ok None = 1 for every resource, db_flags
+    without db_query is OSE_EINVAL), release() returns them, download()
+    copies them, and STAGE_SQLOP runs on DeviceView(released columns).  On an
+    engine without the section they are ignored and released None."""
 
     STATS = ("waiting_traces", "held_spans", "created", "released", "evicted", "released_spans", "added_spans",
              "held_bytes")

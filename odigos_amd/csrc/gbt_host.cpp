@@ -111,6 +111,8 @@ struct Gbt {
   std::vector<uint64_t> wcnt;     // per worker: traces numbered
   std::vector<uint64_t> wrel;     // per worker: its traces with seq < rel_end (released or evicted)
   uint32_t K = 0;
+  bool sql = false;               // the engine has the odigossqldboperationprocessor section: db_flags,
+                                  // db_query and res_sql_ok are carried (else ignored, and released NULL)
   uint64_t pool_cap = 0, scope_cap = 0, arena_cap = 0;
   // device state
   DevMem table, ring, pool, scopes, arena, scratch, sortbuf, out, words, tinfo, wdev;
@@ -283,6 +285,7 @@ GbtArgs base_args(Gbt* g) {
   a.scope_cap = g->scope_cap;
   a.arena_ring = g->arena.p;
   a.arena_cap = g->arena_cap;
+  a.sql = g->sql;
   return a;
 }
 
@@ -323,6 +326,8 @@ int gbt_add(Gbt* g, const ose_columns* c, const uint32_t* attrset_map, int64_t n
   if (!c->trace_id || !c->start_ns || !c->end_ns || !c->status || !c->kind || !c->scope || !c->scope_resource ||
       !c->res_svc || !c->res_attrset || (g->K && (!c->attr_type || !c->attr_val)))
     return fail(OSE_EINVAL, "groupbytrace: a required column is NULL");
+  if (g->sql && c->db_flags && !c->db_query)   // db_query is read wherever a flag has OSE_DB_HAS_QUERY
+    return fail(OSE_EINVAL, "groupbytrace: a required column is NULL (db_flags without db_query)");
   if (g->pool_end - g->pool_begin + n > g->pool_cap || g->scope_end - g->scope_begin + S > g->scope_cap)
     return fail(OSE_ERANGE, "groupbytrace: the store is full (spans waiting for wait_duration exceed its capacity)");
   int rc;
@@ -401,6 +406,7 @@ int gbt_add(Gbt* g, const ose_columns* c, const uint32_t* attrset_map, int64_t n
   launch_gbt_append(a, st);
   launch_gbt_scopes(a, st);
   launch_gbt_strings(a, st);
+  launch_gbt_query_copy(a, st);   // (a store that carries the SQL columns: the queries, a wave at a time)
   HIP_TRY(hipGetLastError());
   uint32_t h[4] = {0, 0, 0, 0};
   HIP_TRY(hipMemcpyAsync(h, g->words.p, 16, hipMemcpyDeviceToHost, st));
@@ -515,11 +521,20 @@ int gbt_release(Gbt* g, int64_t now, hipStream_t st, uint32_t* n_traces) {
         {(void**)&O.res_size, 4 * M}, {(void**)&O.scope_size, 4 * M}, {(void**)&O.scope_resource, 4 * M},
         {(void**)&O.res_url_ok, M},
     };
+    if (g->sql) {
+      parts.push_back({(void**)&O.db_flags, M});
+      parts.push_back({(void**)&O.db_query, 8 * M});
+      parts.push_back({(void**)&O.res_sql_ok, M});
+    }
     size_t total = 0;
     for (auto& p : parts) total = up(total + p.bytes + 16);
     const size_t arena_at = total;
     // the strings of the released spans are at most the live arena bytes
     const size_t arena_bound = g->arena_end - g->arena_begin;
+    // OSE_STAGE_SQLOP reads db_query through 16-byte windows (sqlop_kernel's
+    // ByteReader): it needs a 16-byte aligned arena base and 16 readable
+    // bytes after arena_bytes.  arena_at is a multiple of 256 in a 256-byte
+    // aligned allocation, and 64 bytes follow the last string.
     if ((rc = g->out.need(arena_at + up(arena_bound + 64)))) return rc;
     size_t off = 0;
     for (auto& p : parts) {
@@ -535,6 +550,7 @@ int gbt_release(Gbt* g, int64_t now, hipStream_t st, uint32_t* n_traces) {
     if ((rc = scan_u32(g, a.flag, a.rank, m, totals, st))) return rc;           // fragments
     if ((rc = scan_u32(g, a.strlen, a.stroff, m, totals + 1, st))) return rc;   // string offsets
     launch_gbt_emit(a, st);
+    launch_gbt_block_copy(a, st);   // (a store that carries the SQL columns: emit leaves the bytes to it)
     HIP_TRY(hipGetLastError());
     uint32_t h2[3] = {0, 0, 0};
     HIP_TRY(hipMemcpyAsync(h2, g->words.p, 12, hipMemcpyDeviceToHost, st));
@@ -572,6 +588,11 @@ int gbt_release(Gbt* g, int64_t now, hipStream_t st, uint32_t* n_traces) {
     if (g->K) {
       oc.attr_type = O.attr_type;
       oc.attr_val = O.attr_val;
+    }
+    if (g->sql) {
+      oc.db_flags = O.db_flags;
+      oc.db_query = O.db_query;
+      oc.res_sql_ok = O.res_sql_ok;
     }
   }
   *n_traces = (uint32_t)rel;   // traces with spans in the window (every released trace has >= 1)
@@ -625,6 +646,7 @@ int ose_gbt_create(ose_engine* eng, const char* cfg_json, uint64_t span_capacity
     return fail(OSE_EINVAL, ex.what());
   }
   g->K = (uint32_t)e->attr_keys.size();
+  g->sql = e->has_sqlop;
   g->pool_cap = std::max<uint64_t>(span_capacity, 1024);
   g->scope_cap = g->pool_cap;
   g->arena_cap = std::max<uint64_t>(arena_capacity, 1 << 16);
@@ -646,6 +668,10 @@ int ose_gbt_create(ose_engine* eng, const char* cfg_json, uint64_t span_capacity
       {(void**)&g->P.route, 8 * C}, {(void**)&g->P.path, 8 * C}, {(void**)&g->P.attr_type, K * C + 16},
       {(void**)&g->P.attr_val, 8 * K * C + 16},
   };
+  if (g->sql) {
+    parts.push_back({(void**)&g->P.db_flags, C});
+    parts.push_back({(void**)&g->P.db_query, 8 * C});
+  }
   size_t total = 0;
   for (auto& p : parts) total = up(total + p.bytes + 16);
   const uint64_t SC = g->scope_cap;
@@ -653,6 +679,7 @@ int ose_gbt_create(ose_engine* eng, const char* cfg_json, uint64_t span_capacity
       {(void**)&g->Q.res_svc, 4 * SC}, {(void**)&g->Q.res_svc_str, 4 * SC}, {(void**)&g->Q.res_attrset, 4 * SC},
       {(void**)&g->Q.res_size, 4 * SC}, {(void**)&g->Q.scope_size, 4 * SC}, {(void**)&g->Q.res_url_ok, SC},
   };
+  if (g->sql) sparts.push_back({(void**)&g->Q.res_sql_ok, SC});
   size_t stotal = 0;
   for (auto& p : sparts) stotal = up(stotal + p.bytes + 16);
   int rc;
@@ -737,7 +764,8 @@ int ose_gbt_download(const ose_gbt* gg, const ose_columns* dst) {
       {c.res_url_ok, (void*)dst->res_url_ok, R}, {c.res_attrset, (void*)dst->res_attrset, 4 * R},
       {c.res_size, (void*)dst->res_size, 4 * R}, {c.scope_size, (void*)dst->scope_size, 4 * S},
       {c.scope_resource, (void*)dst->scope_resource, 4 * S}, {c.attr_type, (void*)dst->attr_type, K * n},
-      {c.attr_val, (void*)dst->attr_val, 8 * K * n},
+      {c.attr_val, (void*)dst->attr_val, 8 * K * n}, {c.db_flags, (void*)dst->db_flags, n},
+      {c.db_query, (void*)dst->db_query, 8 * n}, {c.res_sql_ok, (void*)dst->res_sql_ok, R},
   };
   for (auto& f : fs)
     if (f.src && f.dst && f.bytes) HIP_TRY(hipMemcpy(f.dst, f.src, f.bytes, hipMemcpyDefault));

@@ -27,6 +27,15 @@
 //     compacted, stably sorted by seq (arrival order kept inside a trace)
 //     and gathered into fresh columns, one resource and one scope per
 //     fragment (a run of one trace from one scope of one added batch).
+//
+// A store on an engine with the odigossqldboperationprocessor section
+// (GbtArgs::sql) also carries db_flags, db_query and res_sql_ok.  The query
+// bytes are the last string of the span's block.  Routes and paths are a few
+// tens of bytes and move one lane per span; a query is longer (up to KiBs),
+// so the SQL instances move bytes a wave at a time (gbt_query_copy_kernel on
+// the add, gbt_block_copy_kernel on the release).  The kernels are templates
+// on kSql: the <false> instances are the kernels of a store without the
+// section and never read the three columns.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -207,7 +216,24 @@ __global__ __launch_bounds__(kGbtThreads) void gbt_lookup_kernel(GbtArgs a) {
   a.slot_of[i] = gbt_lookup(a, a.cols.trace_id[2 * i], a.cols.trace_id[2 * i + 1], (uint32_t)i);
 }
 
+// OSE_GBT_SQL_PERLANE (an A/B build, odigos_amd/build.py --variant): the SQL
+// instances move the query bytes as the routes are moved, one lane per span
+// and a byte per iteration, and the two wave copies are not launched.  It is
+// the baseline the wave copies were measured against.
+#ifdef OSE_GBT_SQL_PERLANE
+constexpr bool kWaveCopy = false;
+#else
+constexpr bool kWaveCopy = true;
+#endif
+
+// the span's query ref in the added batch: read only under OSE_DB_HAS_QUERY
+__device__ __forceinline__ ose_strref gbt_batch_query(const ose_columns& c, uint64_t i) {
+  if (c.db_flags && (c.db_flags[i] & OSE_DB_HAS_QUERY)) return c.db_query[i];
+  return ose_strref{0, 0};
+}
+
 // creators (the first span of each new trace) and each span's string block length
+template <bool kSql>
 __global__ __launch_bounds__(kGbtThreads) void gbt_creator_kernel(GbtArgs a) {
   const uint64_t i = (uint64_t)blockIdx.x * kGbtThreads + threadIdx.x;
   if (i >= a.n) return;
@@ -224,6 +250,7 @@ __global__ __launch_bounds__(kGbtThreads) void gbt_creator_kernel(GbtArgs a) {
   if (c.path) len += c.path[i].len;
   for (uint32_t k = 0; k < a.n_attr_keys; k++)
     if (c.attr_type[(uint64_t)k * a.n + i] == OSE_ATTR_STR) len += (uint32_t)(c.attr_val[(uint64_t)k * a.n + i] >> 32);
+  if constexpr (kSql) len += gbt_batch_query(c, i).len;
   a.strlen[i] = len;
 }
 
@@ -249,6 +276,7 @@ __global__ __launch_bounds__(kGbtThreads) void gbt_assign_kernel(GbtArgs a) {
 }
 
 // the spans into the pool ring
+template <bool kSql>
 __global__ __launch_bounds__(kGbtThreads) void gbt_append_kernel(GbtArgs a) {
   const uint64_t i = (uint64_t)blockIdx.x * kGbtThreads + threadIdx.x;
   if (i >= a.n || gbt_batch_refused(a)) return;
@@ -269,6 +297,7 @@ __global__ __launch_bounds__(kGbtThreads) void gbt_append_kernel(GbtArgs a) {
   for (uint32_t w = 0; w < a.attr_words; w++)
     P.attr_match[w * a.pool_cap + p] = c.attr_match ? c.attr_match[w * a.n + i] : 0;
   P.origin[p] = a.scope_pos + c.scope[i];
+  if constexpr (kSql) P.db_flags[p] = c.db_flags ? c.db_flags[i] : 0;
 }
 
 __device__ __forceinline__ void ring_copy(uint8_t* ring, uint64_t cap, uint64_t dst, const uint8_t* src, uint32_t n) {
@@ -279,8 +308,98 @@ __device__ __forceinline__ void ring_copy(uint8_t* ring, uint64_t cap, uint64_t 
   }
 }
 
-// the string block: route, path, then the string attribute values; refs in
-// the pool are relative to the block
+// ---- wave copies (the SQL instances) ----------------------------------------
+//
+// One wave takes 64 consecutive spans.  Each lane loads its own span's source,
+// destination and length; the wave then walks the spans that have bytes (a
+// ballot, the owner's values broadcast with v_readlane) and all 64 lanes move
+// that span's bytes, consecutive lanes at consecutive addresses.  No LDS, no
+// atomics, no waiting: every loop runs to a count read once.
+
+__device__ __forceinline__ uint32_t wave_get(uint32_t v, uint32_t owner) {
+  return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)owner);
+}
+__device__ __forceinline__ uint64_t wave_get(uint64_t v, uint32_t owner) {
+  return (uint64_t)wave_get((uint32_t)(v >> 32), owner) << 32 | wave_get((uint32_t)v, owner);
+}
+
+// n bytes src -> dst by the whole wave, neither range wrapping.  Bytes up to
+// the destination's first dword boundary, then one aligned dword store per
+// lane fed by a dword load at the source's own alignment (gfx950 takes a
+// misaligned global load; every byte read is inside [src, src + n)), then
+// the bytes left after the last whole dword.  Right at every src and dst
+// alignment.
+__device__ __forceinline__ void wave_copy(uint8_t* dst, const uint8_t* src, uint32_t n, uint32_t lane) {
+  const uint32_t head = min(n, (uint32_t)(-(uintptr_t)dst & 3u));
+  const uint32_t words = (n - head) >> 2, tail = (n - head) & 3u;
+  if (lane < head) dst[lane] = src[lane];
+  uint32_t* d = reinterpret_cast<uint32_t*>(dst + head);
+  const uint8_t* s = src + head;
+  for (uint32_t k = lane; k < words; k += 64) {
+    uint32_t w;
+    __builtin_memcpy(&w, s + 4ull * k, 4);
+    d[k] = w;
+  }
+  const uint32_t t0 = head + 4 * words;
+  if (lane < tail) dst[t0 + lane] = src[t0 + lane];
+}
+
+// linear src -> the arena ring at position q < arena_cap, wrapping at its end
+__device__ __forceinline__ void wave_copy_in(const GbtArgs& a, uint64_t q, const uint8_t* src, uint32_t n, uint32_t lane) {
+  const uint32_t first = (uint32_t)min<uint64_t>(n, a.arena_cap - q);
+  wave_copy(a.arena_ring + q, src, first, lane);
+  if (first < n) wave_copy(a.arena_ring, src + first, n - first, lane);
+}
+
+// the arena ring from position q < arena_cap, read across its end -> linear dst
+__device__ __forceinline__ void wave_copy_out(const GbtArgs& a, uint8_t* dst, uint64_t q, uint32_t n, uint32_t lane) {
+  const uint32_t first = (uint32_t)min<uint64_t>(n, a.arena_cap - q);
+  wave_copy(dst, a.arena_ring + q, first, lane);
+  if (first < n) wave_copy(dst + first, a.arena_ring, n - first, lane);
+}
+
+// add: the batch's queries into the ring.  A span's query ends its block, so
+// it lies at block + strlen - len (gbt_strings_kernel stores the same ref).
+__global__ __launch_bounds__(kGbtThreads) void gbt_query_copy_kernel(GbtArgs a) {
+  if (gbt_batch_refused(a)) return;
+  const uint64_t i = (uint64_t)blockIdx.x * kGbtThreads + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63u;
+  uint32_t len = 0, off = 0;
+  uint64_t q = 0;
+  if (i < a.n) {
+    const ose_strref x = gbt_batch_query(a.cols, i);
+    off = x.off;
+    len = x.len;
+    q = (a.arena_pos + a.stroff[i] + a.strlen[i] - len) % a.arena_cap;
+  }
+  for (uint64_t todo = __ballot(len != 0); todo; todo &= todo - 1) {
+    const uint32_t o = (uint32_t)__builtin_ctzll(todo);
+    wave_copy_in(a, wave_get(q, o), a.cols.arena + wave_get(off, o), wave_get(len, o), lane);
+  }
+}
+
+// release: the released spans' blocks (route, path, attribute strings, query)
+// out of the ring; consecutive spans' blocks are consecutive in the released
+// arena.  gbt_emit_kernel<true> writes the refs and leaves the bytes to this.
+__global__ __launch_bounds__(kGbtThreads) void gbt_block_copy_kernel(GbtArgs a) {
+  const uint64_t j = (uint64_t)blockIdx.x * kGbtThreads + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63u;
+  uint32_t len = 0, base = 0;
+  uint64_t q = 0;
+  if (j < a.n) {
+    len = a.strlen[j];
+    base = a.stroff[j];
+    q = a.pool.str_off[(a.pool_pos + a.order[j]) % a.pool_cap] % a.arena_cap;
+  }
+  for (uint64_t todo = __ballot(len != 0); todo; todo &= todo - 1) {
+    const uint32_t o = (uint32_t)__builtin_ctzll(todo);
+    wave_copy_out(a, a.out.arena + wave_get(base, o), wave_get(q, o), wave_get(len, o), lane);
+  }
+}
+
+// the string block: route, path, then the string attribute values (kSql: then
+// the query); refs in the pool are relative to the block
+template <bool kSql>
 __global__ __launch_bounds__(kGbtThreads) void gbt_strings_kernel(GbtArgs a) {
   const uint64_t i = (uint64_t)blockIdx.x * kGbtThreads + threadIdx.x;
   if (i >= a.n || gbt_batch_refused(a)) return;
@@ -318,9 +437,16 @@ __global__ __launch_bounds__(kGbtThreads) void gbt_strings_kernel(GbtArgs a) {
     P.attr_type[(uint64_t)k * a.pool_cap + p] = t;
     P.attr_val[(uint64_t)k * a.pool_cap + p] = v;
   }
+  if constexpr (kSql) {
+    const ose_strref x = gbt_batch_query(c, i);
+    const bool has = c.db_flags && (c.db_flags[i] & OSE_DB_HAS_QUERY);
+    if (!kWaveCopy) ring_copy(a.arena_ring, a.arena_cap, blk + rel, c.arena + x.off, x.len);   // else gbt_query_copy_kernel
+    P.db_query[p] = has ? ose_strref{rel, x.len} : ose_strref{0, 0};
+  }
 }
 
 // the batch's scopes into the scope ring, with their resource's columns
+template <bool kSql>
 __global__ __launch_bounds__(kGbtThreads) void gbt_scopes_kernel(GbtArgs a) {
   const uint64_t s = (uint64_t)blockIdx.x * kGbtThreads + threadIdx.x;
   if (s >= a.n_scopes || gbt_batch_refused(a)) return;
@@ -335,6 +461,7 @@ __global__ __launch_bounds__(kGbtThreads) void gbt_scopes_kernel(GbtArgs a) {
   Q.res_attrset[q] = a.attrset_map ? a.attrset_map[set] : set;
   Q.res_size[q] = c.res_size ? c.res_size[r] : 0;
   Q.scope_size[q] = c.scope_size ? c.scope_size[s] : 0;
+  if constexpr (kSql) Q.res_sql_ok[q] = c.res_sql_ok ? c.res_sql_ok[r] : 1;   // NULL: every resource passes
 }
 
 // ---- per-worker numbering (num_workers > 1), after the add's kernels -------
@@ -381,6 +508,7 @@ __global__ __launch_bounds__(kGbtThreads) void gbt_compact_kernel(GbtArgs a) {
 
 // output span j <- pool window position order[j]: fixed columns, fragment
 // heads (a new trace or a new origin scope), string block lengths
+template <bool kSql>
 __global__ __launch_bounds__(kGbtThreads) void gbt_gather_kernel(GbtArgs a) {
   const uint64_t j = (uint64_t)blockIdx.x * kGbtThreads + threadIdx.x;
   if (j >= a.n) return;
@@ -407,10 +535,15 @@ __global__ __launch_bounds__(kGbtThreads) void gbt_gather_kernel(GbtArgs a) {
   for (uint32_t k = 0; k < a.n_attr_keys; k++)
     if (P.attr_type[(uint64_t)k * a.pool_cap + p] == OSE_ATTR_STR)
       len += (uint32_t)(P.attr_val[(uint64_t)k * a.pool_cap + p] >> 32);
+  if constexpr (kSql) {
+    O.db_flags[j] = P.db_flags[p];
+    len += P.db_query[p].len;
+  }
   a.strlen[j] = len;
 }
 
 // strings, refs, resource / scope ids and the fragment columns
+template <bool kSql>
 __global__ __launch_bounds__(kGbtThreads) void gbt_emit_kernel(GbtArgs a) {
   const uint64_t j = (uint64_t)blockIdx.x * kGbtThreads + threadIdx.x;
   if (j >= a.n) return;
@@ -427,10 +560,18 @@ __global__ __launch_bounds__(kGbtThreads) void gbt_emit_kernel(GbtArgs a) {
   for (uint32_t k = 0; k < a.n_attr_keys; k++)
     if (P.attr_type[(uint64_t)k * a.pool_cap + p] == OSE_ATTR_STR)
       total += (uint32_t)(P.attr_val[(uint64_t)k * a.pool_cap + p] >> 32);
-  uint64_t q0 = blk % a.arena_cap;
-  for (uint32_t b = 0; b < total; b++) {
-    O.arena[base + b] = a.arena_ring[q0];
-    if (++q0 == a.arena_cap) q0 = 0;
+  if constexpr (kSql) {
+    const ose_strref x = P.db_query[p];
+    const bool has = P.db_flags[p] & OSE_DB_HAS_QUERY;
+    O.db_query[j] = has ? ose_strref{base + x.off, x.len} : ose_strref{0, 0};
+    total += x.len;
+  }
+  if (!kSql || !kWaveCopy) {   // else gbt_block_copy_kernel moves the block
+    uint64_t q0 = blk % a.arena_cap;
+    for (uint32_t b = 0; b < total; b++) {
+      O.arena[base + b] = a.arena_ring[q0];
+      if (++q0 == a.arena_cap) q0 = 0;
+    }
   }
   const ose_strref r = P.route[p], q = P.path[p];
   O.route[j] = ose_strref{base + r.off, r.len};
@@ -452,6 +593,7 @@ __global__ __launch_bounds__(kGbtThreads) void gbt_emit_kernel(GbtArgs a) {
     O.res_size[f] = Q.res_size[o];
     O.scope_size[f] = Q.scope_size[o];
     O.scope_resource[f] = f;
+    if constexpr (kSql) O.res_sql_ok[f] = Q.res_sql_ok[o];
   }
 }
 
@@ -467,17 +609,29 @@ void launch_gbt_rebuild(const GbtArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(gbt_rebuild_kernel, dim3(b), dim3(kGbtThreads), 0, st, a);
 }
 void launch_gbt_lookup(const GbtArgs& a, hipStream_t st) { GBT_LAUNCH(gbt_lookup_kernel, a.n); }
-void launch_gbt_creator(const GbtArgs& a, hipStream_t st) { GBT_LAUNCH(gbt_creator_kernel, a.n); }
+// the SQL instance on a store that carries the three columns, else the plain one
+#define GBT_LAUNCH_SQL(k, n)         \
+  do {                               \
+    if (a.sql) GBT_LAUNCH(k<true>, n); \
+    else GBT_LAUNCH(k<false>, n);    \
+  } while (0)
+void launch_gbt_creator(const GbtArgs& a, hipStream_t st) { GBT_LAUNCH_SQL(gbt_creator_kernel, a.n); }
 void launch_gbt_assign(const GbtArgs& a, hipStream_t st) { GBT_LAUNCH(gbt_assign_kernel, a.n); }
-void launch_gbt_append(const GbtArgs& a, hipStream_t st) { GBT_LAUNCH(gbt_append_kernel, a.n); }
-void launch_gbt_strings(const GbtArgs& a, hipStream_t st) { GBT_LAUNCH(gbt_strings_kernel, a.n); }
+void launch_gbt_append(const GbtArgs& a, hipStream_t st) { GBT_LAUNCH_SQL(gbt_append_kernel, a.n); }
+void launch_gbt_strings(const GbtArgs& a, hipStream_t st) { GBT_LAUNCH_SQL(gbt_strings_kernel, a.n); }
 void launch_gbt_scopes(const GbtArgs& a, hipStream_t st) {
-  if (a.n_scopes) hipLaunchKernelGGL(gbt_scopes_kernel, dim3(blocks_for(a.n_scopes)), dim3(kGbtThreads), 0, st, a);
+  if (a.n_scopes) GBT_LAUNCH_SQL(gbt_scopes_kernel, a.n_scopes);
 }
 void launch_gbt_flag(const GbtArgs& a, hipStream_t st) { GBT_LAUNCH(gbt_flag_kernel, a.n); }
 void launch_gbt_compact(const GbtArgs& a, hipStream_t st) { GBT_LAUNCH(gbt_compact_kernel, a.n); }
-void launch_gbt_gather(const GbtArgs& a, hipStream_t st) { GBT_LAUNCH(gbt_gather_kernel, a.n); }
-void launch_gbt_emit(const GbtArgs& a, hipStream_t st) { GBT_LAUNCH(gbt_emit_kernel, a.n); }
+void launch_gbt_gather(const GbtArgs& a, hipStream_t st) { GBT_LAUNCH_SQL(gbt_gather_kernel, a.n); }
+void launch_gbt_emit(const GbtArgs& a, hipStream_t st) { GBT_LAUNCH_SQL(gbt_emit_kernel, a.n); }
+void launch_gbt_query_copy(const GbtArgs& a, hipStream_t st) {
+  if (a.sql && kWaveCopy && a.cols.db_flags) GBT_LAUNCH(gbt_query_copy_kernel, a.n);
+}
+void launch_gbt_block_copy(const GbtArgs& a, hipStream_t st) {
+  if (a.sql && kWaveCopy) GBT_LAUNCH(gbt_block_copy_kernel, a.n);
+}
 void launch_gbt_wkey(const GbtArgs& a, hipStream_t st) { GBT_LAUNCH(gbt_wkey_kernel, a.n); }
 void launch_gbt_wnum(const GbtArgs& a, uint64_t created, hipStream_t st) {
   if (created) hipLaunchKernelGGL(gbt_wnum_kernel, dim3(blocks_for(created)), dim3(kGbtThreads), 0, st, a, created);

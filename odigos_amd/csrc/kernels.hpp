@@ -835,10 +835,15 @@ struct GbtPool {              // spans waiting for release (ring of pool_cap)
   ose_strref *route, *path;   // relative to the span's string block
   uint8_t* attr_type;         // key-major, [key * pool_cap + p]
   uint64_t* attr_val;
+  // odigossqldboperationprocessor (GbtArgs::sql; NULL otherwise): the query
+  // is the last string of the block, {0, 0} without OSE_DB_HAS_QUERY
+  uint8_t* db_flags;
+  ose_strref* db_query;
 };
 struct GbtScopes {            // the fragment columns of each added scope (ring)
   uint32_t *res_svc, *res_svc_str, *res_attrset, *res_size, *scope_size;
   uint8_t* res_url_ok;
+  uint8_t* res_sql_ok;        // GbtArgs::sql
 };
 struct GbtOut {               // the released batch
   uint64_t* tid;
@@ -851,6 +856,9 @@ struct GbtOut {               // the released batch
   uint32_t *res_svc, *res_svc_str, *res_attrset, *res_size, *scope_size, *scope_resource;
   uint8_t* res_url_ok;
   uint8_t* arena;
+  uint8_t* db_flags;          // GbtArgs::sql: the three columns of OSE_STAGE_SQLOP
+  ose_strref* db_query;
+  uint8_t* res_sql_ok;
 };
 struct GbtArgs {
   GbtSlot* table;
@@ -894,6 +902,10 @@ struct GbtArgs {
   uint32_t *keys, *vals;
   const uint32_t* order;
   GbtOut out;
+  // the engine has the odigossqldboperationprocessor section: the store
+  // carries db_flags / db_query / res_sql_ok (the launches pick the kernels'
+  // SQL instances; without it they are the instances that never read these)
+  uint32_t sql;
 };
 void launch_gbt_rebuild(const GbtArgs& a, hipStream_t st);
 void launch_gbt_lookup(const GbtArgs& a, hipStream_t st);
@@ -906,6 +918,11 @@ void launch_gbt_flag(const GbtArgs& a, hipStream_t st);
 void launch_gbt_compact(const GbtArgs& a, hipStream_t st);
 void launch_gbt_gather(const GbtArgs& a, hipStream_t st);
 void launch_gbt_emit(const GbtArgs& a, hipStream_t st);
+// GbtArgs::sql only, one wave per 64 spans moving bytes together: the added
+// batch's queries into the arena ring (after launch_gbt_creator's lengths are
+// scanned), the released spans' string blocks out of it (beside launch_gbt_emit)
+void launch_gbt_query_copy(const GbtArgs& a, hipStream_t st);
+void launch_gbt_block_copy(const GbtArgs& a, hipStream_t st);
 void launch_gbt_wkey(const GbtArgs& a, hipStream_t st);                 // creators -> (worker, rank) pairs
 void launch_gbt_wnum(const GbtArgs& a, uint64_t created, hipStream_t st);   // sorted pairs -> tinfo
 
