@@ -65,50 +65,87 @@ __device__ __forceinline__ void rep_slots(const Cfg& c, bool rep, uint32_t slot,
   }
 }
 
+// load_cfg() with the table offsets in scalar registers: read from LDS they
+// arrive in vector registers although every lane reads the same header, and
+// the six table addresses then hold six VGPRs for the whole kernel
+__device__ __forceinline__ Cfg load_cfg_uniform(const uint8_t* b) {
+  Cfg c;
+  c.h = reinterpret_cast<const SampCfgDev*>(b);
+  c.rules = reinterpret_cast<const SampRuleDev*>(b + sgpr(c.h->rules_off));
+  c.lat = reinterpret_cast<const SampLatDev*>(b + sgpr(c.h->lat_off));
+  c.svc_slot = reinterpret_cast<const uint32_t*>(b + sgpr(c.h->svc_slot_off));
+  c.slot_rules = reinterpret_cast<const uint64_t*>(b + sgpr(c.h->slot_rules_off));
+  c.svc_bits = reinterpret_cast<const uint64_t*>(b + sgpr(c.h->svc_bits_off));
+  c.bytes = b + sgpr(c.h->bytes_off);
+  return c;
+}
+
 // ---- per-step columns ---------------------------------------------------------
-// Raw loads of one 64-span step, issued one step ahead of their use (the
-// compiler places the waits at the first use, in the next iteration), so a
-// wave keeps two steps of HBM reads in flight.
+// Raw loads of one 64-span step, issued one step ahead of their use and first
+// waited for at the top of the next iteration, so a wave's column reads of
+// step s+1 are in flight while step s is computed.  vmcnt counts loads in
+// order and the compiler can only count what it can see, so three rules keep
+// a later wait from draining the prefetch (profiles/trace_prefetch_isa.txt):
+//  - values stay as loaded (status is the byte; no conversion or select in
+//    the block that loads);
+//  - no load sits under a divergent branch: the span index is clamped to
+//    n - 1 (a lane past the batch's end reads the last span's columns, which
+//    nothing uses: every use is under valid / mine), and the neighbour trace
+//    id is one load whose address is selected per lane; only wave-uniform
+//    decisions (full, a column that is not configured) branch;
+//  - the step's dependent loads (service ids, route window, route_match) are
+//    consumed before the prefetch is issued (trace_eval_kernel).
 struct StepRaw {
   uint64_t i;          // span index (perm[p] in kTracePerm)
   uint64_t hi, lo;     // trace id
   uint64_t ph, pl;     // lane 0: trace id of position p-1 (head test); lane 63: of p+1 (kTraceRuns)
   uint32_t k, pk;      // kTracePerm: canonical key of p and (lane 0) of p-1
   uint32_t res;
-  uint32_t status;
+  uint8_t status;      // as loaded; widened where it is used
   ose_strref route;
   uint64_t start, end;
   uint64_t svm;        // svc_match (owner-side record columns)
   bool full;           // the per-span columns below the trace id were loaded
 };
+// a value's load has to have arrived here: the wait for it (and, vmcnt being
+// in order, for every load issued before it) is placed at this point
+__device__ __forceinline__ void consume(uint32_t x) { asm volatile("" ::"v"(x)); }
+// Comments in the machine code that tools/vmcnt_report.py reads: the end of
+// the prefetch, and the blocks that run once per many steps and wait for a
+// returning atomic or end in stores (the queue flushes, the long-run
+// hand-off).  No instructions.
+#define OSE_MARK(what) asm volatile("; ose." what)
 // full = false loads only what the head test needs: a wave skipping windows
 // inside a run an earlier wave owns reads 16 B per span, not every column.
-__device__ __forceinline__ StepRaw load_raw(const TraceKernelArgs& a, uint64_t base, int lane, bool full = true) {
+// n_spans > 0 (the callers').
+// res = false leaves the resource index out (trace_eval_kernel's lean
+// instances load it two steps ahead).
+__device__ __forceinline__ StepRaw load_raw(const TraceKernelArgs& a, uint64_t base, int lane, bool full = true,
+                                            bool res = true) {
   StepRaw r{};
   r.full = full;
-  const uint64_t p = base + lane;
-  const bool valid = p < a.n_spans;
-  if (!valid) return r;
+  const uint64_t last = a.n_spans - 1;
+  const uint64_t p = min(base + lane, last);
   if (a.mode == kTracePerm) {
     r.i = a.perm[p];
     r.k = a.key[r.i];
-    if (lane == 0 && p > 0) r.pk = a.key[a.perm[p - 1]];
+    r.pk = a.key[a.perm[p > 0 ? p - 1 : 0]];   // (lane 0's is used)
   } else {
     r.i = p;
-    if (lane == 0 && p > 0 && a.mode == kTraceRuns) {
-      r.ph = a.tid[2 * p - 2];
-      r.pl = a.tid[2 * p - 1];
-    }
-    if (lane == kWave - 1 && p + 1 < a.n_spans && a.mode == kTraceRuns) {   // the span after the step
-      r.ph = a.tid[2 * p + 2];
-      r.pl = a.tid[2 * p + 3];
+    if (a.mode == kTraceRuns) {
+      // lane 0: the span before the step; lane 63: the span after it; the
+      // other lanes read their own id again (the same cache lines)
+      const uint64_t q = lane == 0 ? (p > 0 ? p - 1 : 0) : (lane == kWave - 1 ? min(p + 1, last) : p);
+      const uint4 w = reinterpret_cast<const uint4*>(a.tid)[q];
+      r.ph = (uint64_t)w.x | ((uint64_t)w.y << 32);
+      r.pl = (uint64_t)w.z | ((uint64_t)w.w << 32);
     }
   }
   const uint4 v = reinterpret_cast<const uint4*>(a.tid)[r.i];
   r.hi = (uint64_t)v.x | ((uint64_t)v.y << 32);
   r.lo = (uint64_t)v.z | ((uint64_t)v.w << 32);
   if (!full) return r;
-  r.res = a.resource[r.i];
+  if (res) r.res = a.resource[r.i];
   r.status = a.status[r.i];
   if (a.start) {
     r.start = a.start[r.i];
@@ -116,6 +153,14 @@ __device__ __forceinline__ StepRaw load_raw(const TraceKernelArgs& a, uint64_t b
   }
   if (a.route) r.route = a.route[r.i];
   if (a.svc_match) r.svm = a.svc_match[r.i];
+  return r;
+}
+// The columns of a step whose prefetch was a skip-mode one, loaded at its top
+// and waited for there, all of them (vmcnt(0), the other counters left alone):
+// once per wave, and no later wait then has a load of this step to wait for.
+__device__ __forceinline__ StepRaw reload_raw(const TraceKernelArgs& a, uint64_t base, int lane) {
+  const StepRaw r = load_raw(a, base, lane);
+  __builtin_amdgcn_s_waitcnt(0x0F70);
   return r;
 }
 // head flag of every lane of a step (all lanes take the shuffles)
@@ -152,6 +197,7 @@ __device__ __forceinline__ uint64_t head_fingerprint(uint64_t hi, uint64_t lo) {
 }
 __device__ void flush_heads(const TraceKernelArgs& a, HeadQ& H, uint32_t& hn, int lane) {
   __builtin_amdgcn_wave_barrier();
+  OSE_MARK("flush begin");
   bool dup = false;
   // bucketed: one returning atomic per head, the fingerprint stored after it
   for (uint32_t b = 0; b < hn; b += kWave) {
@@ -165,6 +211,7 @@ __device__ void flush_heads(const TraceKernelArgs& a, HeadQ& H, uint32_t& hn, in
   }
   // one *dup store per wave flush (a per-head atomic on one word serialises)
   if (__ballot(dup) && lane == 0) atomicOr(a.dup, 1u);
+  OSE_MARK("flush end");
   __builtin_amdgcn_wave_barrier();
   hn = 0;
 }
@@ -197,6 +244,7 @@ __device__ __forceinline__ void write_keep_range(const TraceKernelArgs& a, uint6
 __device__ void flush_queue(const TraceKernelArgs& a, const Cfg& c, DecideQ& Q, uint32_t& qn, int lane) {
   if (!qn) return;
   __builtin_amdgcn_wave_barrier();
+  OSE_MARK("flush begin");
   uint8_t dk = 0, dl = 0;
   double dr = 0;
   uint32_t pos = 0, len = 0;
@@ -218,6 +266,7 @@ __device__ void flush_queue(const TraceKernelArgs& a, const Cfg& c, DecideQ& Q, 
     for (uint32_t e = 0; e < qn; e++)
       write_keep_range(a, lane_value(pos, e), lane_value(len, e), (uint8_t)lane_value(dk, e), lane);
   }
+  OSE_MARK("flush end");
   __builtin_amdgcn_wave_barrier();
   qn = 0;
 }
@@ -267,7 +316,7 @@ __global__ __launch_bounds__(kTThreads) __attribute__((amdgpu_waves_per_eu(4, 4)
   const uint64_t wpw = a.win_per_wave;
   const uint64_t w0 = ((uint64_t)blockIdx.x * kTWaves + wv) * wpw;   // first owned window
   if (w0 >= a.n_windows) return;
-  const Cfg c = load_cfg(cfg_lds);
+  const Cfg c = load_cfg_uniform(cfg_lds);
   const uint64_t n = a.n_spans;
   const uint32_t nsvc = c.h->n_services;
 
@@ -304,34 +353,77 @@ __global__ __launch_bounds__(kTThreads) __attribute__((amdgpu_waves_per_eu(4, 4)
   Lat cur{0, kInf, 0};
   uint64_t base = w0 * kWave;
   const bool want_route = c.h->n_lat && !a.route_match && a.route;
-  StepRaw nx = load_raw(a, base, lane);
+  // kPipe (the lean instances: batch order, span index = position): the
+  // dependent chain runs a step ahead of the columns' use.  The resource index
+  // is loaded two steps ahead, the service ids of step s+1 are issued in step
+  // s, in front of its prefetch, and arrive with it: a step waits for the
+  // route window alone.  The pipelined values exist only while the wave
+  // evaluates (a skipped step loads trace ids and nothing else); the first
+  // evaluated step loads its own (prime) and waits.
+  constexpr bool kPipe = kLean;
+  uint32_t p_sv = 0, p_ss = 0, p_res = 0;   // kPipe: service ids of this step, resource index of the next
+  // the columns of the step at b in full, its service ids, the next step's resource index
+  auto prime = [&](uint64_t b) {
+    const StepRaw x = load_raw(a, b, lane);
+    if constexpr (kPipe) {
+      p_res = a.resource[min(b + kWave + lane, n - 1)];
+      p_sv = a.res_svc[x.res];
+      p_ss = a.res_svc_str[x.res];
+    }
+    return x;
+  };
+  StepRaw nx = prime(base);
   for (;;) {
     // Order of the memory operations per step: this step's dependent loads
-    // (resource service ids, the route window, the fingerprint cell), then
-    // the next step's column loads, then the arithmetic — a wait for a load
-    // also waits for every load issued before it (vmcnt counts in order),
-    // so nothing this step consumes may be issued after the prefetch.
+    // (resource service ids unless kPipe, the route window, the fingerprint
+    // cell), then the next step's service ids (kPipe) and column loads, then
+    // the arithmetic — a wait for a load also waits for every load issued
+    // before it (vmcnt counts in order), so nothing this step consumes may be
+    // issued after the prefetch.
     StepRaw r = nx;
     const bool valid = base + lane < n;
     const bool hd = step_head(a, r, base, lane);
     const bool work = started || __ballot(hd) != 0;   // wave-uniform: this step is evaluated
-    if (work && !r.full) r = load_raw(a, base, lane);   // first owned step after skipped ones
-    uint32_t sv = 0xFFFFFFFFu, ss = 0xFFFFFFFFu;
-    uint4 rw = make_uint4(0, 0, 0, 0);
+    if (work && !r.full) {   // first owned step after skipped ones: everything of it, waited for (vmcnt(0))
+      r = prime(base);
+      __builtin_amdgcn_s_waitcnt(0x0F70);
+    }
+    // Everything that reads memory through this step's columns is finished
+    // here, before the prefetch: the service ids, the latency slot, and the
+    // endpoint bits (route window, the bytes of a prefix past it, route_match).
+    uint32_t ss = 0xFFFFFFFFu, slot0 = kNoSlot;
+    uint64_t ep0 = 0;
     if (valid && work) {
-      if (a.ablate & 16) {   // diagnostics: no dependent service-id loads
+      uint32_t sv;
+      if constexpr (kPipe) {
+        sv = p_sv;
+        ss = p_ss;
+      } else if (a.ablate & 16) {   // diagnostics: no dependent service-id loads
         sv = r.res % (nsvc + 1);
         ss = sv;
       } else {
         sv = a.res_svc[r.res];
         ss = a.res_svc_str[r.res];
+        consume(ss);   // (not used before the prefetch otherwise)
       }
-      // route bytes only for spans of a latency-rule service (strings.HasPrefix
-      // is evaluated for nothing else): one dependent LDS lookup, and the
-      // random 16-byte arena reads of every other routed span are skipped
-      if (want_route && r.route.len && sv < nsvc && c.svc_slot[sv] != kNoSlot && !(a.ablate & 32))
-        rw = head16(a.arena, r.route.off, r.route.len);
+      if (sv < nsvc) {
+        slot0 = c.svc_slot[sv];
+        if (slot0 != kNoSlot && !(a.ablate & 8)) {
+          if (a.route_match) {
+            ep0 = a.route_match[r.i] & c.slot_rules[slot0];
+          } else {
+            // route bytes only for spans of a latency-rule service (strings.HasPrefix
+            // is evaluated for nothing else): one dependent LDS lookup, and the
+            // random 16-byte arena reads of every other routed span are skipped
+            uint4 rw = make_uint4(0, 0, 0, 0);
+            if (want_route && r.route.len && !(a.ablate & 32)) rw = head16(a.arena, r.route.off, r.route.len);
+            ep0 = endpoint_bits_w(c, slot0, a.arena, r.route, rw);
+          }
+        }
+      }
     }
+    // kPipe: the youngest load of the last prefetch, so every column of this step is here
+    if constexpr (kPipe) consume(p_res);
     const uint64_t vmask = __ballot(valid);
     const uint64_t hmask = __ballot(hd);
     const bool in_range = base < range_end;
@@ -342,10 +434,19 @@ __global__ __launch_bounds__(kTThreads) __attribute__((amdgpu_waves_per_eu(4, 4)
       if (a.mode == kTraceRuns && !(a.ablate & 1) && a.dup_bkt && hmask)
         queue_heads(a, HQ, hn, hmask, hd, r.hi, r.lo, lane);
     }
-    // (the service ids loaded a step ahead too, the resource index two steps
-    // ahead: C3 -1 %, C4 -1.3 %, C5 +13 % — skipped steps then load every
-    // column; profiles/r4q_te_pipe_ab.txt)
-    if (base + kWave < n) nx = load_raw(a, base + kWave, lane, work);   // prefetch the next step
+    if (base + kWave < n) {   // prefetch the next step
+      if constexpr (kPipe) {
+        if (work) {   // (with a.ablate & 16, diagnostics: no dependent service-id loads)
+          p_sv = (a.ablate & 16) ? p_res % (nsvc + 1) : a.res_svc[p_res];
+          p_ss = (a.ablate & 16) ? p_sv : a.res_svc_str[p_res];
+        }
+      }
+      nx = load_raw(a, base + kWave, lane, work, !kPipe);
+      if constexpr (kPipe) {
+        if (work) p_res = a.resource[min(base + 2 * kWave + lane, n - 1)];
+      }
+    }
+    OSE_MARK("prefetch issued");
     uint64_t own;
     if (in_range) {
       if (!started) {
@@ -387,23 +488,18 @@ __global__ __launch_bounds__(kTThreads) __attribute__((amdgpu_waves_per_eu(4, 4)
     uint64_t ep = 0, svcb = 0, st = 0, en = 0;
     const uint32_t rst = (r.status & kStatusReset) ? 1u : 0u;   // owner-side record: a zero start came first
     if (mine) {
-      const uint32_t s = sv;
-      err = (r.status & ~kStatusReset) == OSE_STATUS_ERROR;
+      err = ((uint32_t)r.status & ~kStatusReset) == OSE_STATUS_ERROR;
       if (a.svc_match) {
         svcb = r.svm;
       } else {
         if (a.mode != kTraceBatch && ss < nsvc) svcb = c.svc_bits[ss];
         if (a.attr_match) svcb |= chunk_attr_bits(a.attr_match, a.attr_stride, a.attr_words, c.h, r.i);
       }
-      if (s < nsvc) {
-        slot = c.svc_slot[s];
-        if (slot != kNoSlot) {
-          if (!(a.ablate & 8))
-            ep = a.route_match ? a.route_match[r.i] & c.slot_rules[slot]
-                               : endpoint_bits_w(c, slot, a.arena, r.route, rw);
-          st = r.start;
-          en = r.end;
-        }
+      slot = slot0;
+      if (slot != kNoSlot) {
+        ep = ep0;
+        st = r.start;
+        en = r.end;
       }
     }
     // ---- latency state (latency.go:69-80) ----
@@ -552,7 +648,9 @@ __global__ __launch_bounds__(kTThreads) __attribute__((amdgpu_waves_per_eu(4, 4)
     if (!open && base >= range_end) break;
     if (open && a.long_runs && base >= range_end + (uint64_t)a.long_steps * kWave) {
       // a long run: trace_long_kernel splits it over a workgroup's waves
+      OSE_MARK("flush begin");   // (the hand-off: the wave's last step)
       if (lane == 0) a.long_runs[atomicAdd(a.n_long, 1u)] = (uint32_t)c_pos;
+      OSE_MARK("flush end");
       break;
     }
   }
@@ -582,6 +680,7 @@ __device__ __forceinline__ void flush_multi(const TraceKernelArgs& a, const uint
                                             const SampWalkDev* walks, MultiQ<K>& Q, uint32_t& qn, int lane) {
   if (!qn) return;
   __builtin_amdgcn_wave_barrier();
+  OSE_MARK("flush begin");
   uint8_t dk = 0, dl = 0;
   double dr = 0;
   uint32_t pos = 0, len = 0;
@@ -603,6 +702,7 @@ __device__ __forceinline__ void flush_multi(const TraceKernelArgs& a, const uint
   } else {
     for (uint32_t e = 0; e < qn; e++) write_keep_range(a, lane_value(pos, e), lane_value(len, e), (uint8_t)lane_value(dk, e), lane);
   }
+  OSE_MARK("flush end");
   __builtin_amdgcn_wave_barrier();
   qn = 0;
 }
@@ -668,12 +768,13 @@ __global__ __launch_bounds__(kTThreads) __attribute__((amdgpu_waves_per_eu(2, 4)
     const bool valid = base + lane < n;
     const bool hd = step_head(a, r, base, lane);
     const bool work = started || __ballot(hd) != 0;   // wave-uniform: this step is evaluated
-    if (work && !r.full) r = load_raw(a, base, lane);
+    if (work && !r.full) r = reload_raw(a, base, lane);
     uint32_t sv = 0xFFFFFFFFu, ss = 0xFFFFFFFFu, gs0 = kNoSlot;
     uint4 rw = make_uint4(0, 0, 0, 0);
     if (valid && work) {
       sv = a.res_svc[r.res];
       ss = a.res_svc_str[r.res];
+      consume(ss);   // (not used before the prefetch otherwise)
       if (sv < nsvc) {
         gs0 = gslot_of[sv];
         // route bytes only for a service with latency rules (in some chunk)
@@ -688,6 +789,7 @@ __global__ __launch_bounds__(kTThreads) __attribute__((amdgpu_waves_per_eu(2, 4)
       if (hmask) queue_heads(a, HQ, hn, hmask, hd, r.hi, r.lo, lane);
     }
     if (base + kWave < n) nx = load_raw(a, base + kWave, lane, work);   // prefetch the next step
+    OSE_MARK("prefetch issued");
     uint64_t own;
     if (in_range) {
       if (!started) {
