@@ -736,6 +736,41 @@ const char* ose_last_error(void);
 /* Runtime facts for diagnostics: device name, gfx arch, CU count. */
 int ose_device_info(char* buf, size_t cap);
 
+/* groupbytrace on the OTLP path: ose_otlp_decode -> ose_gbt_add_otlp ... ->
+ * ose_gbt_release_otlp -> ose_process_device -> ose_otlp_encode, no pdata in
+ * between.
+ *
+ * ose_gbt_add_otlp does what ose_gbt_add does with ose_otlp_columns(b) (same
+ * lookups, numbering, eviction, num_workers, SQL columns, refusals) and also
+ * keeps, in the arena ring, every span's Span message and for every added
+ * scope a header block: the ResourceSpans payload without its scope_spans
+ * fields, then the ScopeSpans payload without its spans fields, every other
+ * top-level field as it stands.  These bytes count toward arena_capacity and
+ * the bytes held; an add they do not fit is OSE_ERANGE with nothing stored.
+ * A store's first successful add fixes its mode: the other add afterwards,
+ * ose_gbt_release / ose_gbt_download on an OTLP-fed store and
+ * ose_gbt_release_otlp on a columns-fed one are OSE_EINVAL, as are a batch of
+ * another engine and a released batch.  An OTLP-fed store takes an
+ * arena_capacity below 2^32 (OSE_ERANGE at the first ose_gbt_add_otlp
+ * otherwise), and a release whose messages would pass 4 GiB is OSE_ERANGE
+ * with nothing released.
+ *
+ * ose_gbt_release_otlp releases the traces ose_gbt_release would, in the same
+ * order.  *out is owned by the store, valid until its next release or
+ * ose_gbt_destroy, and is not to be passed to ose_otlp_release.
+ * ose_otlp_columns(*out) are the columns ose_gbt_release returns, with the
+ * released message buffer as the arena (per fragment its header block, then
+ * each span's message followed by its strings; 256-byte aligned, 64 readable
+ * bytes after arena_bytes).  ose_otlp_encode takes it with every stage mask
+ * and router it takes for a decoded batch; ose_otlp_download works;
+ * ose_otlp_attrset (the ids are the caller's, through attrset_map) and
+ * ose_otlp_timings return OSE_ENOTSUP, ose_otlp_host_spans
+ * (uint32_t)OSE_ENOTSUP.                                                     */
+int ose_gbt_add_otlp(ose_gbt* g, const ose_otlp_batch* b, const uint32_t* attrset_map, int64_t now_ns,
+                     void* hip_stream);
+int ose_gbt_release_otlp(ose_gbt* g, int64_t now_ns, void* hip_stream, const ose_otlp_batch** out,
+                         uint32_t* n_traces);
+
 #ifdef __cplusplus
 }
 #endif

@@ -386,7 +386,12 @@ class GroupByTrace:
     None = 0 for every span, res_sql_ok None = 1 for every resource, db_flags
     without db_query is OSE_EINVAL), release() returns them, download()
     copies them, and STAGE_SQLOP runs on DeviceView(released columns).  On an
-    engine without the section they are ignored and released None."""
+    engine without the section they are ignored and released None.
+
+    On the OTLP path the store is fed with add_otlp(OtlpBatch, ...) and
+    release_otlp() returns a batch whose .encode(...) writes the released
+    traces out (ose_gbt_add_otlp / ose_gbt_release_otlp); a store is fed one
+    way or the other, fixed by its first successful add."""
 
     STATS = ("waiting_traces", "held_spans", "created", "released", "evicted", "released_spans", "added_spans",
              "held_bytes")
@@ -415,6 +420,27 @@ class GroupByTrace:
         s = None if stream is None else C.c_void_p(stream)
         native.check(self.L.ose_gbt_release(self.h, now_ns, s, C.byref(out), C.byref(nt)))
         return native.Columns.from_buffer_copy(out.contents), nt.value
+
+    def add_otlp(self, batch: "OtlpBatch", now_ns: int, attrset_map=None, stream=None):
+        """ose_gbt_add_otlp: add() of the decoded batch's columns, and the store
+        also keeps the spans' messages and the scopes' header blocks so that
+        release_otlp() can hand back batches OtlpBatch.encode writes out.  The
+        first successful add fixes the store's mode (columns or OTLP)."""
+        m = None
+        if attrset_map is not None:
+            m = np.ascontiguousarray(attrset_map, dtype=np.uint32)
+        s = None if stream is None else C.c_void_p(stream)
+        native.check(self.L.ose_gbt_add_otlp(self.h, batch.h, None if m is None else m.ctypes.data, now_ns, s))
+
+    def release_otlp(self, now_ns: int, stream=None, tmpl_cap: int | None = None):
+        """(ReleasedOtlpBatch, traces released): the batch is the store's, valid
+        until the next release or close(); .cols, Engine.process_device and
+        .encode(...) work on it as on a decoded OtlpBatch."""
+        out = C.c_void_p()
+        nt = C.c_uint32()
+        s = None if stream is None else C.c_void_p(stream)
+        native.check(self.L.ose_gbt_release_otlp(self.h, now_ns, s, C.byref(out), C.byref(nt)))
+        return ReleasedOtlpBatch(self, out, tmpl_cap), nt.value
 
     def stats(self) -> dict:
         v = (C.c_uint64 * 8)()
@@ -540,6 +566,27 @@ class OtlpBatch:
             self.h = None
 
     __del__ = close
+
+
+class ReleasedOtlpBatch(OtlpBatch):
+    """The batch a groupbytrace store released (GroupByTrace.release_otlp): a
+    view of the store's handle.  close() releases nothing; the store frees it."""
+
+    def __init__(self, store: "GroupByTrace", h, tmpl_cap: int | None = None):
+        self.L = store.L
+        self.eng = store.eng
+        self.store = store   # the handle lives as long as the store
+        self.h = h
+        self.cols = native.Columns.from_buffer_copy(self.L.ose_otlp_columns(h).contents)
+        self.outs, self.o = device_outputs(self.cols, tmpl_cap=tmpl_cap)
+
+    def close(self):
+        self.h = None
+
+    __del__ = close
+
+
+GbtStore = GroupByTrace
 
 
 class OtlpPipeline:

@@ -49,6 +49,35 @@ struct OtlpEngine;
 void release_otlp(Engine* e);                      // otlp_host.cpp
 void release_encode(Engine* e);                    // otlp_encode.cpp
 
+// What the groupbytrace store (gbt_host.cpp) reads of a decoded ose_otlp_batch
+// and writes into the one it releases (otlp_host.cpp owns the type).
+struct OtlpBatchView {
+  Engine* e;
+  const ose_columns* cols;
+  bool released;                 // a store's released batch (not to be added again)
+  const uint64_t* d_spans;       // [n_spans] Span payload refs (device)
+  // the ResourceSpans / ScopeSpans payload refs: on the device when the GPU
+  // walked the ResourceSpans level, else host arrays
+  bool res_on_device;
+  const uint64_t *d_res_ref, *d_scope_ref;
+  const uint64_t *h_res_ref, *h_scope_ref;
+  size_t h_res_n, h_scope_n;
+};
+void otlp_batch_view(const ose_otlp_batch* b, OtlpBatchView* v);
+struct OtlpReleasedLayout {      // device arrays, as the GPU encoder reads them
+  const uint64_t* spans;
+  const uint32_t* span0;
+  const uint64_t *hdr, *schema;
+  const uint64_t* res_ref;
+  const uint32_t* res_scope0;
+  const uint64_t* scope_ref;
+};
+ose_otlp_batch* otlp_released_new(Engine* e);      // holds no engine reference: the store does
+void otlp_released_delete(ose_otlp_batch* b);
+// the released message buffer: at least `bytes`, 256-byte aligned
+int otlp_released_arena(ose_otlp_batch* b, size_t bytes, uint8_t** p);
+void otlp_released_set(ose_otlp_batch* b, const ose_columns& cols, const OtlpReleasedLayout& lay);
+
 // Device scratch for one in-flight call (look-back status words, sort
 // buffers, partial records).  Engines keep a pool so concurrent callers never
 // share one.

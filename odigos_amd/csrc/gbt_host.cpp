@@ -116,6 +116,24 @@ struct Gbt {
   uint64_t pool_cap = 0, scope_cap = 0, arena_cap = 0;
   // device state
   DevMem table, ring, pool, scopes, arena, scratch, sortbuf, out, words, tinfo, wdev;
+  // The first successful add fixes the mode: columns (ose_gbt_add) or OTLP
+  // (ose_gbt_add_otlp: the blocks start with the Span message, every added
+  // scope has a header block; omem holds the rings' extra columns and `rel`
+  // is the batch ose_gbt_release_otlp hands out, owned here)
+  enum Mode { kUnset, kColumns, kOtlp } mode = kUnset;
+  DevMem omem;
+  GbtOtlp O2{};
+  ose_otlp_batch* rel = nullptr;
+  // diagnostics (osehost_gbt_copy_times): HIP events around the two OTLP wave
+  // copies, the message copy of the last add and the block copy of the last release
+  bool time_copies = false;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  float copy_ms[2] = {0, 0};
+  ~Gbt() {
+    if (rel) otlp_released_delete(rel);
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
   uint64_t table_slots = 0;
   uint32_t epoch = 0;
   GbtPool P{};
@@ -286,6 +304,11 @@ GbtArgs base_args(Gbt* g) {
   a.arena_ring = g->arena.p;
   a.arena_cap = g->arena_cap;
   a.sql = g->sql;
+  if (g->mode == Gbt::kOtlp) {
+    a.otlp = g->O2;
+    a.otlp.on = 1;
+    a.otlp.total64 = reinterpret_cast<uint64_t*>(g->words.p + 40);
+  }
   return a;
 }
 
@@ -316,10 +339,40 @@ int number_workers(Gbt* g, GbtArgs a, uint64_t created, hipStream_t st) {
   return 0;
 }
 
-int gbt_add(Gbt* g, const ose_columns* c, const uint32_t* attrset_map, int64_t now, hipStream_t st) {
+// the rings' OTLP columns, at the first ose_gbt_add_otlp
+int otlp_rings(Gbt* g) {
+  if (g->omem.p) return 0;
+  const uint64_t C = g->pool_cap, SC = g->scope_cap;
+  if (int rc = g->omem.need(up(4 * C + 16) + up(8 * SC + 16) + 2 * up(4 * SC + 16))) return rc;
+  uint8_t* p = g->omem.p;
+  g->O2.msg_len = reinterpret_cast<uint32_t*>(p);
+  p += up(4 * C + 16);
+  g->O2.hdr_off = reinterpret_cast<uint64_t*>(p);
+  p += up(8 * SC + 16);
+  g->O2.hdr_res = reinterpret_cast<uint32_t*>(p);
+  p += up(4 * SC + 16);
+  g->O2.hdr_scope = reinterpret_cast<uint32_t*>(p);
+  return 0;
+}
+
+// v: the decoded batch behind `c` (ose_gbt_add_otlp), NULL for ose_gbt_add
+int gbt_add(Gbt* g, const ose_columns* c, const uint32_t* attrset_map, int64_t now, hipStream_t st,
+            const OtlpBatchView* v = nullptr) {
+  const Gbt::Mode want = v ? Gbt::kOtlp : Gbt::kColumns;
+  if (g->mode != Gbt::kUnset && g->mode != want)
+    return fail(OSE_EINVAL, v ? "groupbytrace: ose_gbt_add_otlp on a store that ose_gbt_add has fed"
+                              : "groupbytrace: ose_gbt_add on a store that ose_gbt_add_otlp has fed");
   if (now < g->last_now) return fail(OSE_EINVAL, "groupbytrace: now_ns went backwards");
   const uint64_t n = c->n_spans, S = c->n_scopes;
   if (!n) return 0;
+  if (v) {
+    // offsets into the ring and into a release are scanned as uint32
+    if (g->arena_cap >= (1ull << 32))
+      return fail(OSE_ERANGE, "groupbytrace: an OTLP-fed store takes an arena_capacity below 2^32");
+    if (!v->d_spans || !c->arena || (v->res_on_device ? !v->d_res_ref || !v->d_scope_ref
+                                                       : v->h_res_n != c->n_resources || v->h_scope_n != S))
+      return fail(OSE_EINVAL, "groupbytrace: the OTLP batch has no message layout");
+  }
   if (g->K && c->n_attr_keys != g->K) return fail(OSE_EINVAL, "groupbytrace: the batch's attribute key columns differ from the engine's");
   if (c->attr_match && std::max<uint32_t>(1, c->attr_match_words) != g->e->attr_words)
     return fail(OSE_EINVAL, "groupbytrace: attr_match_words differs from the engine's span_attribute rule words");
@@ -357,9 +410,21 @@ int gbt_add(Gbt* g, const ose_columns* c, const uint32_t* attrset_map, int64_t n
   // attribute-set map; W > 1: the (worker, rank) pairs (4n each)
   const size_t A = c->n_attrsets;
   const size_t wpairs = g->W > 1 ? 2 * up(4 * n + 16) : 0;
-  if ((rc = g->scratch.need(up(8 * n) + 4 * up(4 * n + 16) + up(4 * A + 16) + wpairs)) ||
-      (rc = words_need(g, std::max<uint64_t>(n, g->W))))
+  // OTLP: the scopes' header lengths (two parts, sum, scan) and, where the
+  // decoder left them on the host, the ResourceSpans / ScopeSpans refs
+  const uint64_t R = c->n_resources;
+  const size_t hdrs = v ? 4 * up(4 * S + 16) + up(8 * R + 16) + up(8 * S + 16) : 0;
+  if ((rc = g->scratch.need(up(8 * n) + 4 * up(4 * n + 16) + up(4 * A + 16) + wpairs + hdrs)) ||
+      (rc = words_need(g, std::max<uint64_t>(std::max<uint64_t>(n, g->W), v ? S : 0))) || (v && (rc = otlp_rings(g))))
     return rc;
+  const Gbt::Mode mode0 = g->mode;
+  g->mode = want;   // base_args picks the instances; put back unless the add succeeds
+  struct ModeGuard {
+    Gbt* g;
+    Gbt::Mode m;
+    bool keep = false;
+    ~ModeGuard() { if (!keep) g->mode = m; }
+  } guard{g, mode0};
   GbtArgs a = base_args(g);
   a.slot_of = reinterpret_cast<uint64_t*>(g->scratch.p);
   a.flag = reinterpret_cast<uint32_t*>(g->scratch.p + up(8 * n));
@@ -379,6 +444,25 @@ int gbt_add(Gbt* g, const ose_columns* c, const uint32_t* attrset_map, int64_t n
     // the workers' counts before the batch: its lookups and the rebuild skip evicted traces
     HIP_TRY(hipMemcpyAsync(g->wdev.p, g->wcnt.data(), 8ull * g->W, hipMemcpyHostToDevice, st));
   }
+  if (v) {
+    uint32_t* h0 = dmap + up(4 * A + 16) / 4 + wpairs / 4;
+    a.otlp.hres = h0;
+    a.otlp.hscope = h0 + up(4 * S + 16) / 4;
+    a.otlp.hlen = h0 + 2 * (up(4 * S + 16) / 4);
+    a.otlp.hoff = h0 + 3 * (up(4 * S + 16) / 4);
+    uint64_t* rr = reinterpret_cast<uint64_t*>(h0 + 4 * (up(4 * S + 16) / 4));
+    uint64_t* sr = rr + up(8 * R + 16) / 8;
+    a.otlp.span_ref = v->d_spans;
+    if (v->res_on_device) {
+      a.otlp.res_ref = v->d_res_ref;
+      a.otlp.scope_ref = v->d_scope_ref;
+    } else {   // (pageable sources: the copies are staged before the calls return)
+      if (R) HIP_TRY(hipMemcpyAsync(rr, v->h_res_ref, 8 * R, hipMemcpyHostToDevice, st));
+      if (S) HIP_TRY(hipMemcpyAsync(sr, v->h_scope_ref, 8 * S, hipMemcpyHostToDevice, st));
+      a.otlp.res_ref = rr;
+      a.otlp.scope_ref = sr;
+    }
+  }
   a.cols = *c;
   a.n = n;
   a.n_scopes = S;
@@ -391,15 +475,22 @@ int gbt_add(Gbt* g, const ose_columns* c, const uint32_t* attrset_map, int64_t n
   a.arena_pos = g->arena_end;
   a.arena_room = g->arena_cap - (g->arena_end - g->arena_begin);
   HIP_TRY(hipMemsetAsync(g->words.p, 0, 16, st));   // error word, totals
+  if (v) HIP_TRY(hipMemsetAsync(g->words.p + 36, 0, 12, st));   // header bytes (u32 scan total), all bytes (u64)
   uint32_t* totals = reinterpret_cast<uint32_t*>(g->words.p) + 1;   // [0] new traces, [1] string bytes
   a.totals = totals;
   (void)hipGetLastError();
   if (rebuild) launch_gbt_rebuild(a, st);
   launch_gbt_lookup(a, st);
+  if (v) launch_gbt_hdr_len(a, st);
   launch_gbt_creator(a, st);
   HIP_TRY(hipGetLastError());
   if ((rc = scan_u32(g, a.flag, a.rank, n, totals, st))) return rc;
   if ((rc = scan_u32(g, a.strlen, a.stroff, n, totals + 1, st))) return rc;
+  if (v) {
+    if ((rc = scan_u32(g, a.otlp.hlen, a.otlp.hoff, S, reinterpret_cast<uint32_t*>(g->words.p) + 9, st))) return rc;
+    launch_gbt_total(a, st);
+    HIP_TRY(hipGetLastError());
+  }
   // every kernel from here stores nothing when the batch's strings do not
   // fit the arena ring (error bit 8): a refused add leaves the store as it was
   launch_gbt_assign(a, st);
@@ -407,12 +498,23 @@ int gbt_add(Gbt* g, const ose_columns* c, const uint32_t* attrset_map, int64_t n
   launch_gbt_scopes(a, st);
   launch_gbt_strings(a, st);
   launch_gbt_query_copy(a, st);   // (a store that carries the SQL columns: the queries, a wave at a time)
+  if (v) {
+    if (g->time_copies) HIP_TRY(hipEventRecord(g->ev[0], st));
+    launch_gbt_msg_copy(a, st);   // the Span messages, a wave at a time; the scopes' header blocks
+    if (g->time_copies) HIP_TRY(hipEventRecord(g->ev[1], st));
+    launch_gbt_hdr_copy(a, st);
+  }
   HIP_TRY(hipGetLastError());
-  uint32_t h[4] = {0, 0, 0, 0};
-  HIP_TRY(hipMemcpyAsync(h, g->words.p, 16, hipMemcpyDeviceToHost, st));
+  uint32_t h[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(h, g->words.p, v ? 48 : 16, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
+  if (v && g->time_copies) HIP_TRY(hipEventElapsedTime(&g->copy_ms[0], g->ev[0], g->ev[1]));
   if (rebuild) g->slots_used = live;
   g->table_valid = true;
+  if (h[0] & 16u) {   // (nothing stored: the kernels treat it as a refusal)
+    g->slots_used += n;
+    return fail(OSE_EINVAL, "groupbytrace: a ResourceSpans or ScopeSpans header the store cannot carry (malformed, or a group)");
+  }
   if (h[0] & 8u) {
     g->slots_used += n;   // ids the lookups claimed stay as tombstones
     return fail(OSE_ERANGE, "groupbytrace: the string arena is full (bytes waiting for wait_duration exceed its capacity)");
@@ -421,7 +523,10 @@ int gbt_add(Gbt* g, const ose_columns* c, const uint32_t* attrset_map, int64_t n
     g->table_valid = false;
     return fail(OSE_EDEVICE, "groupbytrace: device table error " + std::to_string(h[0]));
   }
-  const uint64_t created = h[1], bytes = h[2];
+  uint64_t total64;
+  std::memcpy(&total64, h + 10, 8);
+  const uint64_t created = h[1], bytes = v ? total64 : h[2];
+  guard.keep = true;
   if (g->W > 1 && created && (rc = number_workers(g, a, created, st))) {
     g->table_valid = false;
     return rc;
@@ -440,12 +545,15 @@ int gbt_add(Gbt* g, const ose_columns* c, const uint32_t* attrset_map, int64_t n
   return 0;
 }
 
-int gbt_release(Gbt* g, int64_t now, hipStream_t st, uint32_t* n_traces) {
+// otlp: ose_gbt_release_otlp (the released batch g->rel gets the columns and the layout)
+int gbt_release(Gbt* g, int64_t now, hipStream_t st, uint32_t* n_traces, bool otlp = false) {
   if (now < g->last_now) return fail(OSE_EINVAL, "groupbytrace: now_ns went backwards");
   g->last_now = now;
   ose_columns& oc = g->out_cols;
   oc = ose_columns{};
   *n_traces = 0;
+  OtlpReleasedLayout lay{};
+  if (otlp) otlp_released_set(g->rel, oc, lay);   // an empty batch unless spans leave below
   // traces whose timer has fired: those created by the expired epochs
   size_t k = 0;
   uint64_t b = g->rel_end;
@@ -526,11 +634,24 @@ int gbt_release(Gbt* g, int64_t now, hipStream_t st, uint32_t* n_traces) {
       parts.push_back({(void**)&O.db_query, 8 * M});
       parts.push_back({(void**)&O.res_sql_ok, M});
     }
+    if (otlp) {   // what the GPU encoder reads: per span, per fragment (at most m)
+      GbtOtlp& X = a.otlp;
+      parts.push_back({(void**)&X.out_span_ref, 8 * M});
+      parts.push_back({(void**)&X.out_span0, 4 * M});
+      parts.push_back({(void**)&X.out_res_scope0, 4 * M});
+      parts.push_back({(void**)&X.out_hdr, 8 * M});
+      parts.push_back({(void**)&X.out_schema, 8 * M});
+      parts.push_back({(void**)&X.out_res_ref, 8 * M});
+      parts.push_back({(void**)&X.out_scope_ref, 8 * M});
+    }
     size_t total = 0;
     for (auto& p : parts) total = up(total + p.bytes + 16);
     const size_t arena_at = total;
     // the strings of the released spans are at most the live arena bytes
-    const size_t arena_bound = g->arena_end - g->arena_begin;
+    // (OTLP: a header block leaves once per released fragment, so the live
+    // bytes are no bound; the message buffer is the released batch's own and
+    // is sized from the fragment scan below)
+    const size_t arena_bound = otlp ? 0 : g->arena_end - g->arena_begin;
     // OSE_STAGE_SQLOP reads db_query through 16-byte windows (sqlop_kernel's
     // ByteReader): it needs a 16-byte aligned arena base and 16 readable
     // bytes after arena_bytes.  arena_at is a multiple of 256 in a 256-byte
@@ -549,14 +670,37 @@ int gbt_release(Gbt* g, int64_t now, hipStream_t st, uint32_t* n_traces) {
     HIP_TRY(hipGetLastError());
     if ((rc = scan_u32(g, a.flag, a.rank, m, totals, st))) return rc;           // fragments
     if ((rc = scan_u32(g, a.strlen, a.stroff, m, totals + 1, st))) return rc;   // string offsets
+    uint64_t msg_bytes = 0;
+    uint32_t frags = 0;
+    if (otlp) {
+      // the buffer's size in 64 bits and the fragments, read before a byte moves
+      HIP_TRY(hipMemsetAsync(a.otlp.total64, 0, 8, st));
+      a.n_scopes = 0;
+      launch_gbt_total(a, st);
+      HIP_TRY(hipGetLastError());
+      uint32_t h1[12];
+      HIP_TRY(hipMemcpyAsync(h1, g->words.p, 48, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      if (h1[0]) return fail(OSE_EDEVICE, "groupbytrace: device error " + std::to_string(h1[0]));
+      frags = h1[1];
+      std::memcpy(&msg_bytes, h1 + 10, 8);
+      if (msg_bytes > 0xFFFFFF00ull)   // the u32 offsets above have wrapped: nothing is moved
+        return fail(OSE_ERANGE, "groupbytrace: the released messages exceed the 4 GiB a batch's refs can address");
+      if ((rc = otlp_released_arena(g->rel, up(msg_bytes + 64), &O.arena))) return rc;
+      HIP_TRY(hipMemsetAsync(O.arena + msg_bytes, 0, 64, st));
+    }
     launch_gbt_emit(a, st);
+    if (otlp && g->time_copies) HIP_TRY(hipEventRecord(g->ev[2], st));
     launch_gbt_block_copy(a, st);   // (a store that carries the SQL columns: emit leaves the bytes to it)
+    if (otlp && g->time_copies) HIP_TRY(hipEventRecord(g->ev[3], st));
+    if (otlp) launch_gbt_frag_hdr(a, frags, st);
     HIP_TRY(hipGetLastError());
     uint32_t h2[3] = {0, 0, 0};
     HIP_TRY(hipMemcpyAsync(h2, g->words.p, 12, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    if (otlp && g->time_copies) HIP_TRY(hipEventElapsedTime(&g->copy_ms[1], g->ev[2], g->ev[3]));
     if (h2[0]) return fail(OSE_EDEVICE, "groupbytrace: device error " + std::to_string(h2[0]));
-    const uint32_t F = h2[1], bytes = h2[2];
+    const uint32_t F = h2[1], bytes = otlp ? (uint32_t)msg_bytes : h2[2];
     oc.n_spans = m;
     oc.n_resources = F;
     oc.n_scopes = F;
@@ -593,6 +737,12 @@ int gbt_release(Gbt* g, int64_t now, hipStream_t st, uint32_t* n_traces) {
       oc.db_flags = O.db_flags;
       oc.db_query = O.db_query;
       oc.res_sql_ok = O.res_sql_ok;
+    }
+    if (otlp) {
+      const GbtOtlp& X = a.otlp;
+      lay = OtlpReleasedLayout{X.out_span_ref, X.out_span0, X.out_hdr, X.out_schema, X.out_res_ref, X.out_res_scope0,
+                               X.out_scope_ref};
+      otlp_released_set(g->rel, oc, lay);
     }
   }
   *n_traces = (uint32_t)rel;   // traces with spans in the window (every released trace has >= 1)
@@ -721,9 +871,36 @@ int ose_gbt_add(ose_gbt* gg, const ose_columns* cols, const uint32_t* attrset_ma
   return gbt_add(g, cols, attrset_map, now_ns, static_cast<hipStream_t>(hip_stream));
 }
 
+int ose_gbt_add_otlp(ose_gbt* gg, const ose_otlp_batch* b, const uint32_t* attrset_map, int64_t now_ns,
+                     void* hip_stream) {
+  if (!gg || !b) return fail(OSE_EINVAL, "NULL argument");
+  auto* g = reinterpret_cast<Gbt*>(gg);
+  OtlpBatchView v;
+  otlp_batch_view(b, &v);
+  if (v.e != g->e) return fail(OSE_EINVAL, "groupbytrace: the batch belongs to another engine");
+  if (v.released) return fail(OSE_EINVAL, "groupbytrace: a released batch cannot be added");
+  if (int rc = bind_device(g->e)) return rc;
+  return gbt_add(g, v.cols, attrset_map, now_ns, static_cast<hipStream_t>(hip_stream), &v);
+}
+
+int ose_gbt_release_otlp(ose_gbt* gg, int64_t now_ns, void* hip_stream, const ose_otlp_batch** out,
+                         uint32_t* n_traces) {
+  if (!gg || !out || !n_traces) return fail(OSE_EINVAL, "NULL argument");
+  auto* g = reinterpret_cast<Gbt*>(gg);
+  if (g->mode == Gbt::kColumns)
+    return fail(OSE_EINVAL, "groupbytrace: ose_gbt_release_otlp on a store that ose_gbt_add has fed (use ose_gbt_release)");
+  if (int rc = bind_device(g->e)) return rc;
+  if (!g->rel) g->rel = otlp_released_new(g->e);
+  const int rc = gbt_release(g, now_ns, static_cast<hipStream_t>(hip_stream), n_traces, true);
+  *out = g->rel;
+  return rc;
+}
+
 int ose_gbt_release(ose_gbt* gg, int64_t now_ns, void* hip_stream, const ose_columns** out, uint32_t* n_traces) {
   if (!gg || !out || !n_traces) return fail(OSE_EINVAL, "NULL argument");
   auto* g = reinterpret_cast<Gbt*>(gg);
+  if (g->mode == Gbt::kOtlp)
+    return fail(OSE_EINVAL, "groupbytrace: ose_gbt_release on a store that ose_gbt_add_otlp has fed (use ose_gbt_release_otlp)");
   if (int rc = bind_device(g->e)) return rc;
   const int rc = gbt_release(g, now_ns, static_cast<hipStream_t>(hip_stream), n_traces);
   *out = &g->out_cols;
@@ -748,6 +925,8 @@ int ose_gbt_stats(const ose_gbt* gg, uint64_t* out8) {
 int ose_gbt_download(const ose_gbt* gg, const ose_columns* dst) {
   if (!gg || !dst) return fail(OSE_EINVAL, "NULL argument");
   const auto* g = reinterpret_cast<const Gbt*>(gg);
+  if (g->mode == Gbt::kOtlp)
+    return fail(OSE_EINVAL, "groupbytrace: ose_gbt_download on a store that ose_gbt_add_otlp has fed (use ose_otlp_download)");
   if (int rc = bind_device(g->e)) return rc;
   const ose_columns& c = g->out_cols;
   const uint64_t n = c.n_spans, R = c.n_resources, S = c.n_scopes, K = c.n_attr_keys;
@@ -769,6 +948,25 @@ int ose_gbt_download(const ose_gbt* gg, const ose_columns* dst) {
   };
   for (auto& f : fs)
     if (f.src && f.dst && f.bytes) HIP_TRY(hipMemcpy(f.dst, f.src, f.bytes, hipMemcpyDefault));
+  return 0;
+}
+
+// Diagnostics (tools/gbt_otlp_bench.py): on != 0 turns on HIP events around an
+// OTLP-fed store's two wave copies; ms2 (may be NULL) receives the time of
+// gbt_msg_copy_kernel in the last add and of gbt_block_copy_kernel in the
+// last release
+int osehost_gbt_copy_times(ose_gbt* gg, int on, double* ms2) {
+  if (!gg) return fail(OSE_EINVAL, "NULL argument");
+  auto* g = reinterpret_cast<Gbt*>(gg);
+  if (int rc = bind_device(g->e)) return rc;
+  if (on)
+    for (hipEvent_t& e : g->ev)
+      if (!e) HIP_TRY(hipEventCreate(&e));
+  g->time_copies = on != 0;
+  if (ms2) {
+    ms2[0] = g->copy_ms[0];
+    ms2[1] = g->copy_ms[1];
+  }
   return 0;
 }
 

@@ -36,11 +36,26 @@
 // the add, gbt_block_copy_kernel on the release).  The kernels are templates
 // on kSql: the <false> instances are the kernels of a store without the
 // section and never read the three columns.
+//
+// A store fed by ose_gbt_add_otlp (GbtArgs::otlp, template parameter kOtlp)
+// also keeps what ose_otlp_encode needs to write a released span out again:
+// a span's block starts with its Span message (every ref of the block shifts
+// by the message's length; the query stays last), and every added scope has a
+// header block in the ring, after the add's span blocks: its ResourceSpans
+// payload without the scope_spans fields, then its ScopeSpans payload without
+// the spans fields.  The release lays out, per fragment, the header block and
+// then the spans' blocks, and writes the layout arrays the encoder reads.
+// Messages are a few hundred bytes: gbt_msg_copy_kernel (add) and
+// gbt_block_copy_kernel<true> (release) move them a wave at a time with
+// 16-byte stores.  Offsets are 32-bit scans; gbt_total_kernel sums the same
+// lengths in 64 bits, and that total decides refusals and sizes.  The
+// <., false> instances are the kernels of a columns-fed store.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
 
+#include "pb_device.hpp"      // Rd: the header blocks' top-level fields (OTLP mode)
 #include "trace_device.hpp"   // tid_hash: the trace table's hash
 
 namespace ose {
@@ -233,7 +248,7 @@ __device__ __forceinline__ ose_strref gbt_batch_query(const ose_columns& c, uint
 }
 
 // creators (the first span of each new trace) and each span's string block length
-template <bool kSql>
+template <bool kSql, bool kOtlp>
 __global__ __launch_bounds__(kGbtThreads) void gbt_creator_kernel(GbtArgs a) {
   const uint64_t i = (uint64_t)blockIdx.x * kGbtThreads + threadIdx.x;
   if (i >= a.n) return;
@@ -251,19 +266,24 @@ __global__ __launch_bounds__(kGbtThreads) void gbt_creator_kernel(GbtArgs a) {
   for (uint32_t k = 0; k < a.n_attr_keys; k++)
     if (c.attr_type[(uint64_t)k * a.n + i] == OSE_ATTR_STR) len += (uint32_t)(c.attr_val[(uint64_t)k * a.n + i] >> 32);
   if constexpr (kSql) len += gbt_batch_query(c, i).len;
+  if constexpr (kOtlp) len += (uint32_t)(a.otlp.span_ref[i] >> 32);   // the message leads the block
   a.strlen[i] = len;
 }
 
 // the batch's strings do not fit the arena ring: nothing of the batch is
 // stored (no trace numbered, no ring slot overwritten) and the add fails
+// (OTLP mode: blocks and header blocks, summed in 64 bits)
+template <bool kOtlp = false>
 __device__ __forceinline__ bool gbt_batch_refused(const GbtArgs& a) {
+  if constexpr (kOtlp) return a.otlp.total64[0] > a.arena_room || (a.error[0] & 16u);   // 16: a header not walked
   return (uint64_t)a.totals[1] > a.arena_room;
 }
 
 // new traces numbered in first-appearance order; the ring remembers their ids
+template <bool kOtlp>
 __global__ __launch_bounds__(kGbtThreads) void gbt_assign_kernel(GbtArgs a) {
   const uint64_t i = (uint64_t)blockIdx.x * kGbtThreads + threadIdx.x;
-  if (gbt_batch_refused(a)) {
+  if (gbt_batch_refused<kOtlp>(a)) {
     if (i == 0) atomicOr(a.error, 8u);
     return;
   }
@@ -276,10 +296,10 @@ __global__ __launch_bounds__(kGbtThreads) void gbt_assign_kernel(GbtArgs a) {
 }
 
 // the spans into the pool ring
-template <bool kSql>
+template <bool kSql, bool kOtlp>
 __global__ __launch_bounds__(kGbtThreads) void gbt_append_kernel(GbtArgs a) {
   const uint64_t i = (uint64_t)blockIdx.x * kGbtThreads + threadIdx.x;
-  if (i >= a.n || gbt_batch_refused(a)) return;
+  if (i >= a.n || gbt_batch_refused<kOtlp>(a)) return;
   const GbtPool& P = a.pool;
   const ose_columns& c = a.cols;
   const uint64_t p = (a.pool_pos + i) % a.pool_cap;
@@ -344,24 +364,57 @@ __device__ __forceinline__ void wave_copy(uint8_t* dst, const uint8_t* src, uint
   if (lane < tail) dst[t0 + lane] = src[t0 + lane];
 }
 
+// The OTLP instances' move: messages are a few hundred bytes, so the middle
+// goes as aligned 16-byte stores (one per lane, 1 KiB per wave step) fed by
+// 16-byte loads at the source's own alignment; up to 15 bytes before the
+// destination's first 16-byte boundary and after the last whole 16 go a byte
+// per lane.  Every byte read is inside [src, src + n).
+__device__ __forceinline__ void wave_copy16(uint8_t* dst, const uint8_t* src, uint32_t n, uint32_t lane) {
+  const uint32_t head = min(n, (uint32_t)(-(uintptr_t)dst & 15u));
+  const uint32_t quads = (n - head) >> 4, tail = (n - head) & 15u;
+  if (lane < head) dst[lane] = src[lane];
+  uint4* d = reinterpret_cast<uint4*>(dst + head);
+  const uint8_t* s = src + head;
+  for (uint32_t k = lane; k < quads; k += 64) {
+    uint4 w;
+    __builtin_memcpy(&w, s + 16ull * k, 16);
+    d[k] = w;
+  }
+  const uint32_t t0 = head + 16 * quads;
+  if (lane < tail) dst[t0 + lane] = src[t0 + lane];
+}
+
 // linear src -> the arena ring at position q < arena_cap, wrapping at its end
+template <bool kWide = false>
 __device__ __forceinline__ void wave_copy_in(const GbtArgs& a, uint64_t q, const uint8_t* src, uint32_t n, uint32_t lane) {
   const uint32_t first = (uint32_t)min<uint64_t>(n, a.arena_cap - q);
-  wave_copy(a.arena_ring + q, src, first, lane);
-  if (first < n) wave_copy(a.arena_ring, src + first, n - first, lane);
+  if constexpr (kWide) {
+    wave_copy16(a.arena_ring + q, src, first, lane);
+    if (first < n) wave_copy16(a.arena_ring, src + first, n - first, lane);
+  } else {
+    wave_copy(a.arena_ring + q, src, first, lane);
+    if (first < n) wave_copy(a.arena_ring, src + first, n - first, lane);
+  }
 }
 
 // the arena ring from position q < arena_cap, read across its end -> linear dst
+template <bool kWide = false>
 __device__ __forceinline__ void wave_copy_out(const GbtArgs& a, uint8_t* dst, uint64_t q, uint32_t n, uint32_t lane) {
   const uint32_t first = (uint32_t)min<uint64_t>(n, a.arena_cap - q);
-  wave_copy(dst, a.arena_ring + q, first, lane);
-  if (first < n) wave_copy(dst + first, a.arena_ring, n - first, lane);
+  if constexpr (kWide) {
+    wave_copy16(dst, a.arena_ring + q, first, lane);
+    if (first < n) wave_copy16(dst + first, a.arena_ring, n - first, lane);
+  } else {
+    wave_copy(dst, a.arena_ring + q, first, lane);
+    if (first < n) wave_copy(dst + first, a.arena_ring, n - first, lane);
+  }
 }
 
 // add: the batch's queries into the ring.  A span's query ends its block, so
 // it lies at block + strlen - len (gbt_strings_kernel stores the same ref).
+template <bool kOtlp>
 __global__ __launch_bounds__(kGbtThreads) void gbt_query_copy_kernel(GbtArgs a) {
-  if (gbt_batch_refused(a)) return;
+  if (gbt_batch_refused<kOtlp>(a)) return;
   const uint64_t i = (uint64_t)blockIdx.x * kGbtThreads + threadIdx.x;
   const uint32_t lane = threadIdx.x & 63u;
   uint32_t len = 0, off = 0;
@@ -381,34 +434,173 @@ __global__ __launch_bounds__(kGbtThreads) void gbt_query_copy_kernel(GbtArgs a) 
 // release: the released spans' blocks (route, path, attribute strings, query)
 // out of the ring; consecutive spans' blocks are consecutive in the released
 // arena.  gbt_emit_kernel<true> writes the refs and leaves the bytes to this.
+// OTLP mode: the block starts with the span's message, and a fragment's
+// first span has the fragment's header block moved ahead of its own.
+template <bool kOtlp>
 __global__ __launch_bounds__(kGbtThreads) void gbt_block_copy_kernel(GbtArgs a) {
   const uint64_t j = (uint64_t)blockIdx.x * kGbtThreads + threadIdx.x;
   const uint32_t lane = threadIdx.x & 63u;
-  uint32_t len = 0, base = 0;
-  uint64_t q = 0;
+  uint32_t len = 0, base = 0, hlen = 0;
+  uint64_t q = 0, hq = 0;
   if (j < a.n) {
     len = a.strlen[j];
     base = a.stroff[j];
-    q = a.pool.str_off[(a.pool_pos + a.order[j]) % a.pool_cap] % a.arena_cap;
+    const uint64_t p = (a.pool_pos + a.order[j]) % a.pool_cap;
+    q = a.pool.str_off[p] % a.arena_cap;
+    if constexpr (kOtlp) {
+      if (a.flag[j]) {
+        const uint64_t o = a.pool.origin[p] % a.scope_cap;
+        hlen = a.otlp.hdr_res[o] + a.otlp.hdr_scope[o];
+        hq = a.otlp.hdr_off[o] % a.arena_cap;
+        len -= hlen;   // gbt_gather_kernel counted the header with the span
+      }
+    }
+  }
+  if constexpr (kOtlp) {
+    for (uint64_t todo = __ballot(hlen != 0); todo; todo &= todo - 1) {
+      const uint32_t o = (uint32_t)__builtin_ctzll(todo);
+      wave_copy_out<true>(a, a.out.arena + wave_get(base, o), wave_get(hq, o), wave_get(hlen, o), lane);
+    }
+    base += hlen;
   }
   for (uint64_t todo = __ballot(len != 0); todo; todo &= todo - 1) {
     const uint32_t o = (uint32_t)__builtin_ctzll(todo);
-    wave_copy_out(a, a.out.arena + wave_get(base, o), wave_get(q, o), wave_get(len, o), lane);
+    wave_copy_out<kOtlp>(a, a.out.arena + wave_get(base, o), wave_get(q, o), wave_get(len, o), lane);
   }
+}
+
+// ---- OTLP mode: messages and header blocks -----------------------------------
+
+// add: the batch's Span messages to the head of their blocks, a wave per 64
+// consecutive spans and all 64 lanes on one message (as gbt_query_copy_kernel)
+__global__ __launch_bounds__(kGbtThreads) void gbt_msg_copy_kernel(GbtArgs a) {
+  if (gbt_batch_refused<true>(a)) return;
+  const uint64_t i = (uint64_t)blockIdx.x * kGbtThreads + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63u;
+  uint32_t len = 0, off = 0;
+  uint64_t q = 0;
+  if (i < a.n) {
+    const uint64_t ref = a.otlp.span_ref[i];
+    off = (uint32_t)ref;
+    len = (uint32_t)(ref >> 32);
+    q = (a.arena_pos + a.stroff[i]) % a.arena_cap;
+  }
+  for (uint64_t todo = __ballot(len != 0); todo; todo &= todo - 1) {
+    const uint32_t o = (uint32_t)__builtin_ctzll(todo);
+    wave_copy_in<true>(a, wave_get(q, o), a.cols.arena + wave_get(off, o), wave_get(len, o), lane);
+  }
+}
+
+// The top-level fields of the payload [s, e) other than the LEN field `drop`
+// (ResourceSpans.scope_spans, ScopeSpans.spans: both field 2): their bytes,
+// and with kCopy each field as it stands into the ring from position *dst on.
+// false: malformed (the decoder walked these payloads, so a bug).
+template <bool kCopy>
+__device__ bool gbt_hdr_fields(const GbtArgs& a, uint32_t s, uint32_t e, uint32_t* bytes, uint64_t* dst) {
+  pbdev::Rd r(a.cols.arena, s, e);
+  uint32_t total = 0;
+  while (r.more()) {
+    const uint32_t f0 = r.i;
+    uint32_t f, wt;
+    if (!r.tag(f, wt) || !r.skip(wt)) break;
+    if (f == 2 && wt == 2) continue;
+    const uint32_t n = r.i - f0;
+    if constexpr (kCopy) {
+      uint64_t q = *dst % a.arena_cap;
+      for (uint32_t b = 0; b < n; b++) {
+        a.arena_ring[q] = a.cols.arena[f0 + b];
+        if (++q == a.arena_cap) q = 0;
+      }
+      *dst += n;
+    }
+    total += n;
+  }
+  *bytes = total;
+  return !r.bad;
+}
+
+// add: every added scope's header lengths, one lane per scope
+__global__ __launch_bounds__(kGbtThreads) void gbt_hdr_len_kernel(GbtArgs a) {
+  const uint64_t s = (uint64_t)blockIdx.x * kGbtThreads + threadIdx.x;
+  if (s >= a.n_scopes) return;
+  const uint64_t rr = a.otlp.res_ref[a.cols.scope_resource[s]], sr = a.otlp.scope_ref[s];
+  uint32_t hr = 0, hs = 0;
+  const bool ok = gbt_hdr_fields<false>(a, (uint32_t)rr, (uint32_t)rr + (uint32_t)(rr >> 32), &hr, nullptr) &&
+                  gbt_hdr_fields<false>(a, (uint32_t)sr, (uint32_t)sr + (uint32_t)(sr >> 32), &hs, nullptr);
+  if (!ok) {
+    atomicOr(a.error, 16u);
+    hr = hs = 0;
+  }
+  a.otlp.hres[s] = hr;
+  a.otlp.hscope[s] = hs;
+  a.otlp.hlen[s] = hr + hs;
+}
+
+// ... and their bytes into the ring, after the call's span blocks
+__global__ __launch_bounds__(kGbtThreads) void gbt_hdr_copy_kernel(GbtArgs a) {
+  const uint64_t s = (uint64_t)blockIdx.x * kGbtThreads + threadIdx.x;
+  if (s >= a.n_scopes || gbt_batch_refused<true>(a) || !a.otlp.hlen[s]) return;
+  const uint64_t rr = a.otlp.res_ref[a.cols.scope_resource[s]], sr = a.otlp.scope_ref[s];
+  uint64_t dst = a.arena_pos + a.totals[1] + a.otlp.hoff[s];
+  uint32_t n;
+  gbt_hdr_fields<true>(a, (uint32_t)rr, (uint32_t)rr + (uint32_t)(rr >> 32), &n, &dst);
+  gbt_hdr_fields<true>(a, (uint32_t)sr, (uint32_t)sr + (uint32_t)(sr >> 32), &n, &dst);
+}
+
+// The bytes of the call in 64 bits: strlen[0, n) and, on the add, hlen[0,
+// n_scopes).  The u32 scans give the offsets; this total decides the refusal
+// and sizes the release, so a wrapped scan total is never acted on.  One
+// atomic per wave.
+__global__ __launch_bounds__(kGbtThreads) void gbt_total_kernel(GbtArgs a) {
+  uint64_t sum = 0;
+  const uint64_t stride = (uint64_t)gridDim.x * kGbtThreads;
+  for (uint64_t i = (uint64_t)blockIdx.x * kGbtThreads + threadIdx.x; i < a.n; i += stride) sum += a.strlen[i];
+  for (uint64_t s = (uint64_t)blockIdx.x * kGbtThreads + threadIdx.x; s < a.n_scopes; s += stride) sum += a.otlp.hlen[s];
+  for (int d = 32; d; d >>= 1) sum += __shfl_down(sum, d, 64);
+  if ((threadIdx.x & 63u) == 0 && sum) atomicAdd(reinterpret_cast<unsigned long long*>(a.otlp.total64), (unsigned long long)sum);
+}
+
+// release: each fragment's InstrumentationScope and schema_url refs from its
+// moved ScopeSpans part, by the decoder's rule (otlp_scope_count_kernel): the
+// scope field, kOtlpScopeMulti when several, the last schema_url
+__global__ __launch_bounds__(kGbtThreads) void gbt_frag_hdr_kernel(GbtArgs a, uint64_t n_frag) {
+  const uint64_t f = (uint64_t)blockIdx.x * kGbtThreads + threadIdx.x;
+  if (f >= n_frag) return;
+  const uint64_t ref = a.otlp.out_scope_ref[f];
+  pbdev::Rd r(a.out.arena, (uint32_t)ref, (uint32_t)ref + (uint32_t)(ref >> 32));
+  uint64_t hdr = 0, schema = 0;
+  uint32_t nh = 0, fld, wt;
+  while (r.more() && r.tag(fld, wt)) {
+    uint32_t ps, pl;
+    if (fld == 1 || fld == 3) {
+      if (wt != 2 || !r.len(ps, pl)) { r.bad = true; break; }
+      if (fld == 1) { hdr = (uint64_t)ps | ((uint64_t)pl << 32); nh++; }
+      else schema = (uint64_t)ps | ((uint64_t)pl << 32);
+    } else {
+      r.skip(wt);
+    }
+  }
+  if (r.bad) atomicOr(a.error, 16u);
+  a.otlp.out_hdr[f] = nh > 1 ? kOtlpScopeMulti : hdr;
+  a.otlp.out_schema[f] = schema;
 }
 
 // the string block: route, path, then the string attribute values (kSql: then
 // the query); refs in the pool are relative to the block
-template <bool kSql>
+template <bool kSql, bool kOtlp>
 __global__ __launch_bounds__(kGbtThreads) void gbt_strings_kernel(GbtArgs a) {
   const uint64_t i = (uint64_t)blockIdx.x * kGbtThreads + threadIdx.x;
-  if (i >= a.n || gbt_batch_refused(a)) return;
+  if (i >= a.n || gbt_batch_refused<kOtlp>(a)) return;
   const GbtPool& P = a.pool;
   const ose_columns& c = a.cols;
   const uint64_t p = (a.pool_pos + i) % a.pool_cap;
   const uint64_t blk = a.arena_pos + a.stroff[i];
   P.str_off[p] = blk;
   uint32_t rel = 0;
+  if constexpr (kOtlp) {   // the message first (gbt_msg_copy_kernel moves it): every ref below shifts by its length
+    rel = (uint32_t)(a.otlp.span_ref[i] >> 32);
+    a.otlp.msg_len[p] = rel;
+  }
   ose_strref r{0, 0};
   if (c.route) {
     const ose_strref x = c.route[i];
@@ -446,10 +638,10 @@ __global__ __launch_bounds__(kGbtThreads) void gbt_strings_kernel(GbtArgs a) {
 }
 
 // the batch's scopes into the scope ring, with their resource's columns
-template <bool kSql>
+template <bool kSql, bool kOtlp>
 __global__ __launch_bounds__(kGbtThreads) void gbt_scopes_kernel(GbtArgs a) {
   const uint64_t s = (uint64_t)blockIdx.x * kGbtThreads + threadIdx.x;
-  if (s >= a.n_scopes || gbt_batch_refused(a)) return;
+  if (s >= a.n_scopes || gbt_batch_refused<kOtlp>(a)) return;
   const ose_columns& c = a.cols;
   const GbtScopes& Q = a.scopes;
   const uint64_t q = (a.scope_pos + s) % a.scope_cap;
@@ -462,6 +654,11 @@ __global__ __launch_bounds__(kGbtThreads) void gbt_scopes_kernel(GbtArgs a) {
   Q.res_size[q] = c.res_size ? c.res_size[r] : 0;
   Q.scope_size[q] = c.scope_size ? c.scope_size[s] : 0;
   if constexpr (kSql) Q.res_sql_ok[q] = c.res_sql_ok ? c.res_sql_ok[r] : 1;   // NULL: every resource passes
+  if constexpr (kOtlp) {   // the header blocks follow the call's span blocks (totals[1] bytes: not refused, so no wrap)
+    a.otlp.hdr_off[q] = a.arena_pos + a.totals[1] + a.otlp.hoff[s];
+    a.otlp.hdr_res[q] = a.otlp.hres[s];
+    a.otlp.hdr_scope[q] = a.otlp.hscope[s];
+  }
 }
 
 // ---- per-worker numbering (num_workers > 1), after the add's kernels -------
@@ -508,7 +705,7 @@ __global__ __launch_bounds__(kGbtThreads) void gbt_compact_kernel(GbtArgs a) {
 
 // output span j <- pool window position order[j]: fixed columns, fragment
 // heads (a new trace or a new origin scope), string block lengths
-template <bool kSql>
+template <bool kSql, bool kOtlp>
 __global__ __launch_bounds__(kGbtThreads) void gbt_gather_kernel(GbtArgs a) {
   const uint64_t j = (uint64_t)blockIdx.x * kGbtThreads + threadIdx.x;
   if (j >= a.n) return;
@@ -539,11 +736,18 @@ __global__ __launch_bounds__(kGbtThreads) void gbt_gather_kernel(GbtArgs a) {
     O.db_flags[j] = P.db_flags[p];
     len += P.db_query[p].len;
   }
+  if constexpr (kOtlp) {   // the message, and ahead of a fragment's first span its header block
+    len += a.otlp.msg_len[p];
+    if (head) {
+      const uint64_t o = P.origin[p] % a.scope_cap;
+      len += a.otlp.hdr_res[o] + a.otlp.hdr_scope[o];
+    }
+  }
   a.strlen[j] = len;
 }
 
 // strings, refs, resource / scope ids and the fragment columns
-template <bool kSql>
+template <bool kSql, bool kOtlp>
 __global__ __launch_bounds__(kGbtThreads) void gbt_emit_kernel(GbtArgs a) {
   const uint64_t j = (uint64_t)blockIdx.x * kGbtThreads + threadIdx.x;
   if (j >= a.n) return;
@@ -553,7 +757,19 @@ __global__ __launch_bounds__(kGbtThreads) void gbt_emit_kernel(GbtArgs a) {
   const uint32_t f = a.rank[j] + a.flag[j] - 1;   // fragment index (inclusive scan - 1)
   O.resource[j] = f;
   O.scope[j] = f;
-  const uint32_t base = a.stroff[j];
+  uint32_t base = a.stroff[j];
+  if constexpr (kOtlp) {
+    if (a.flag[j]) {   // the fragment's header block, then this span's block
+      const uint64_t o = P.origin[p] % a.scope_cap;
+      const uint32_t hr = a.otlp.hdr_res[o], hs = a.otlp.hdr_scope[o];
+      a.otlp.out_res_ref[f] = (uint64_t)base | (uint64_t)hr << 32;
+      a.otlp.out_scope_ref[f] = (uint64_t)(base + hr) | (uint64_t)hs << 32;
+      a.otlp.out_span0[f] = (uint32_t)j;
+      a.otlp.out_res_scope0[f] = f;
+      base += hr + hs;
+    }
+    a.otlp.out_span_ref[j] = (uint64_t)base | (uint64_t)a.otlp.msg_len[p] << 32;
+  }
   const uint64_t blk = P.str_off[p];
   const uint32_t len = P.route[p].len + P.path[p].len;
   uint32_t total = len;
@@ -566,7 +782,7 @@ __global__ __launch_bounds__(kGbtThreads) void gbt_emit_kernel(GbtArgs a) {
     O.db_query[j] = has ? ose_strref{base + x.off, x.len} : ose_strref{0, 0};
     total += x.len;
   }
-  if (!kSql || !kWaveCopy) {   // else gbt_block_copy_kernel moves the block
+  if (!kOtlp && (!kSql || !kWaveCopy)) {   // else gbt_block_copy_kernel moves the block
     uint64_t q0 = blk % a.arena_cap;
     for (uint32_t b = 0; b < total; b++) {
       O.arena[base + b] = a.arena_ring[q0];
@@ -609,28 +825,49 @@ void launch_gbt_rebuild(const GbtArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(gbt_rebuild_kernel, dim3(b), dim3(kGbtThreads), 0, st, a);
 }
 void launch_gbt_lookup(const GbtArgs& a, hipStream_t st) { GBT_LAUNCH(gbt_lookup_kernel, a.n); }
-// the SQL instance on a store that carries the three columns, else the plain one
-#define GBT_LAUNCH_SQL(k, n)         \
-  do {                               \
-    if (a.sql) GBT_LAUNCH(k<true>, n); \
-    else GBT_LAUNCH(k<false>, n);    \
+// the SQL instance on a store that carries the three columns, else the plain
+// one; the OTLP instance on a store fed by ose_gbt_add_otlp
+#define GBT_LAUNCH_MODE(k, n)                                                                 \
+  do {                                                                                        \
+    void (*fn)(GbtArgs) = a.otlp.on ? (a.sql ? k<true, true> : k<false, true>)                \
+                                    : (a.sql ? k<true, false> : k<false, false>);             \
+    hipLaunchKernelGGL(fn, dim3(blocks_for(n)), dim3(kGbtThreads), 0, st, a);                 \
   } while (0)
-void launch_gbt_creator(const GbtArgs& a, hipStream_t st) { GBT_LAUNCH_SQL(gbt_creator_kernel, a.n); }
-void launch_gbt_assign(const GbtArgs& a, hipStream_t st) { GBT_LAUNCH(gbt_assign_kernel, a.n); }
-void launch_gbt_append(const GbtArgs& a, hipStream_t st) { GBT_LAUNCH_SQL(gbt_append_kernel, a.n); }
-void launch_gbt_strings(const GbtArgs& a, hipStream_t st) { GBT_LAUNCH_SQL(gbt_strings_kernel, a.n); }
+#define GBT_LAUNCH_OTLP(k, n)                                                                 \
+  do {                                                                                        \
+    void (*fn)(GbtArgs) = a.otlp.on ? k<true> : k<false>;                                     \
+    hipLaunchKernelGGL(fn, dim3(blocks_for(n)), dim3(kGbtThreads), 0, st, a);                 \
+  } while (0)
+void launch_gbt_creator(const GbtArgs& a, hipStream_t st) { GBT_LAUNCH_MODE(gbt_creator_kernel, a.n); }
+void launch_gbt_assign(const GbtArgs& a, hipStream_t st) { GBT_LAUNCH_OTLP(gbt_assign_kernel, a.n); }
+void launch_gbt_append(const GbtArgs& a, hipStream_t st) { GBT_LAUNCH_MODE(gbt_append_kernel, a.n); }
+void launch_gbt_strings(const GbtArgs& a, hipStream_t st) { GBT_LAUNCH_MODE(gbt_strings_kernel, a.n); }
 void launch_gbt_scopes(const GbtArgs& a, hipStream_t st) {
-  if (a.n_scopes) GBT_LAUNCH_SQL(gbt_scopes_kernel, a.n_scopes);
+  if (a.n_scopes) GBT_LAUNCH_MODE(gbt_scopes_kernel, a.n_scopes);
 }
 void launch_gbt_flag(const GbtArgs& a, hipStream_t st) { GBT_LAUNCH(gbt_flag_kernel, a.n); }
 void launch_gbt_compact(const GbtArgs& a, hipStream_t st) { GBT_LAUNCH(gbt_compact_kernel, a.n); }
-void launch_gbt_gather(const GbtArgs& a, hipStream_t st) { GBT_LAUNCH_SQL(gbt_gather_kernel, a.n); }
-void launch_gbt_emit(const GbtArgs& a, hipStream_t st) { GBT_LAUNCH_SQL(gbt_emit_kernel, a.n); }
+void launch_gbt_gather(const GbtArgs& a, hipStream_t st) { GBT_LAUNCH_MODE(gbt_gather_kernel, a.n); }
+void launch_gbt_emit(const GbtArgs& a, hipStream_t st) { GBT_LAUNCH_MODE(gbt_emit_kernel, a.n); }
 void launch_gbt_query_copy(const GbtArgs& a, hipStream_t st) {
-  if (a.sql && kWaveCopy && a.cols.db_flags) GBT_LAUNCH(gbt_query_copy_kernel, a.n);
+  if (a.sql && kWaveCopy && a.cols.db_flags) GBT_LAUNCH_OTLP(gbt_query_copy_kernel, a.n);
 }
 void launch_gbt_block_copy(const GbtArgs& a, hipStream_t st) {
-  if (a.sql && kWaveCopy) GBT_LAUNCH(gbt_block_copy_kernel, a.n);
+  if (a.otlp.on || (a.sql && kWaveCopy)) GBT_LAUNCH_OTLP(gbt_block_copy_kernel, a.n);
+}
+void launch_gbt_hdr_len(const GbtArgs& a, hipStream_t st) {
+  if (a.n_scopes) GBT_LAUNCH(gbt_hdr_len_kernel, a.n_scopes);
+}
+void launch_gbt_total(const GbtArgs& a, hipStream_t st) {
+  const uint64_t n = std::max(a.n, a.n_scopes);
+  if (n) hipLaunchKernelGGL(gbt_total_kernel, dim3(std::min<uint32_t>(blocks_for(n), 1024)), dim3(kGbtThreads), 0, st, a);
+}
+void launch_gbt_msg_copy(const GbtArgs& a, hipStream_t st) { GBT_LAUNCH(gbt_msg_copy_kernel, a.n); }
+void launch_gbt_hdr_copy(const GbtArgs& a, hipStream_t st) {
+  if (a.n_scopes) GBT_LAUNCH(gbt_hdr_copy_kernel, a.n_scopes);
+}
+void launch_gbt_frag_hdr(const GbtArgs& a, uint64_t n_frag, hipStream_t st) {
+  if (n_frag) hipLaunchKernelGGL(gbt_frag_hdr_kernel, dim3(blocks_for(n_frag)), dim3(kGbtThreads), 0, st, a, n_frag);
 }
 void launch_gbt_wkey(const GbtArgs& a, hipStream_t st) { GBT_LAUNCH(gbt_wkey_kernel, a.n); }
 void launch_gbt_wnum(const GbtArgs& a, uint64_t created, hipStream_t st) {

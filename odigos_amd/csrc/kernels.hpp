@@ -860,6 +860,28 @@ struct GbtOut {               // the released batch
   ose_strref* db_query;
   uint8_t* res_sql_ok;
 };
+// OTLP mode (ose_gbt_add_otlp / ose_gbt_release_otlp): a span's block in the
+// arena ring is [Span message][strings as in columns mode], and every added
+// scope has a header block there too: its ResourceSpans payload without the
+// scope_spans fields, then its ScopeSpans payload without the spans fields.
+struct GbtOtlp {
+  uint32_t on;                  // the launches pick the kernels' OTLP instances
+  // add: the batch's layout (device), per-scope header lengths and their scan
+  const uint64_t* span_ref;     // [n] Span payload off | len << 32 in cols.arena
+  const uint64_t* res_ref;      // [n_resources] ResourceSpans payload
+  const uint64_t* scope_ref;    // [n_scopes] ScopeSpans payload
+  uint32_t *hres, *hscope;      // [n_scopes] bytes of the two header parts
+  uint32_t *hlen, *hoff;        // [n_scopes] their sum, its exclusive scan
+  uint64_t* total64;            // [0] bytes of the call's blocks and header blocks (never wraps)
+  // the rings
+  uint32_t* msg_len;            // pool: the message is the first msg_len bytes of the block
+  uint64_t* hdr_off;            // scope ring: the header block's arena position
+  uint32_t *hdr_res, *hdr_scope;   // scope ring: bytes of its two parts
+  // release: what the GPU encoder reads, per span / per fragment
+  uint64_t* out_span_ref;
+  uint32_t *out_span0, *out_res_scope0;
+  uint64_t *out_hdr, *out_schema, *out_res_ref, *out_scope_ref;
+};
 struct GbtArgs {
   GbtSlot* table;
   uint64_t table_mask;
@@ -906,6 +928,9 @@ struct GbtArgs {
   // carries db_flags / db_query / res_sql_ok (the launches pick the kernels'
   // SQL instances; without it they are the instances that never read these)
   uint32_t sql;
+  // a store fed by ose_gbt_add_otlp (at the end: the fields above keep their
+  // offsets, and a columns-mode store never reads these)
+  GbtOtlp otlp;
 };
 void launch_gbt_rebuild(const GbtArgs& a, hipStream_t st);
 void launch_gbt_lookup(const GbtArgs& a, hipStream_t st);
@@ -923,6 +948,15 @@ void launch_gbt_emit(const GbtArgs& a, hipStream_t st);
 // scanned), the released spans' string blocks out of it (beside launch_gbt_emit)
 void launch_gbt_query_copy(const GbtArgs& a, hipStream_t st);
 void launch_gbt_block_copy(const GbtArgs& a, hipStream_t st);
+// OTLP mode: the added scopes' header lengths (before their scan); the call's
+// byte total in 64 bits (n = spans of the add, or released spans); the
+// messages and header blocks into the ring; the released fragments'
+// InstrumentationScope / schema_url refs out of their moved header blocks
+void launch_gbt_hdr_len(const GbtArgs& a, hipStream_t st);
+void launch_gbt_total(const GbtArgs& a, hipStream_t st);
+void launch_gbt_msg_copy(const GbtArgs& a, hipStream_t st);
+void launch_gbt_hdr_copy(const GbtArgs& a, hipStream_t st);
+void launch_gbt_frag_hdr(const GbtArgs& a, uint64_t n_frag, hipStream_t st);
 void launch_gbt_wkey(const GbtArgs& a, hipStream_t st);                 // creators -> (worker, rank) pairs
 void launch_gbt_wnum(const GbtArgs& a, uint64_t created, hipStream_t st);   // sorted pairs -> tinfo
 

@@ -216,7 +216,12 @@ struct OtlpBatchImpl {
   bool scopes_dev = false;
   DevBuf eslab, eout, emisc;
   DevBuf seth;   // pinned: the resource pass's attribute-set scan words and ids (read after the scope pass's wait)
-  OtlpBatchImpl() { stage.host = true; emisc.host = true; seth.host = true; }
+  // a batch released by a groupbytrace store (ose_gbt_release_otlp): the
+  // store owns it, `arena` is the released message buffer and every layout
+  // array is the store's; relhost takes the buffer when the host encoder runs
+  bool released = false;
+  DevBuf relhost;
+  OtlpBatchImpl() { stage.host = true; emisc.host = true; seth.host = true; relhost.host = true; }
 };
 
 
@@ -1765,6 +1770,58 @@ int encode_gpu(OtlpBatchImpl* b, const ose_outputs* outs, bool sampled, bool tmp
 }
 }  // namespace
 
+// ---- batches of the groupbytrace store (gbt_host.cpp) ---------------------------
+void otlp_batch_view(const ose_otlp_batch* bb, OtlpBatchView* v) {
+  const auto* b = reinterpret_cast<const OtlpBatchImpl*>(bb);
+  *v = OtlpBatchView{};
+  v->e = b->e;
+  v->cols = &b->cols;
+  v->released = b->released;
+  v->d_spans = b->d_spans;
+  v->res_on_device = b->res_on_device;
+  v->d_res_ref = b->d_res_ref;
+  v->d_scope_ref = b->d_scope_ref;
+  v->h_res_ref = b->lay.res_ref.data();
+  v->h_res_n = b->lay.res_ref.size();
+  v->h_scope_ref = b->lay.scope_ref.data();
+  v->h_scope_n = b->lay.scope_ref.size();
+}
+
+ose_otlp_batch* otlp_released_new(Engine* e) {
+  auto* b = new OtlpBatchImpl();
+  b->e = e;
+  b->released = true;
+  return reinterpret_cast<ose_otlp_batch*>(b);
+}
+
+void otlp_released_delete(ose_otlp_batch* bb) { delete reinterpret_cast<OtlpBatchImpl*>(bb); }
+
+int otlp_released_arena(ose_otlp_batch* bb, size_t bytes, uint8_t** p) {
+  auto* b = reinterpret_cast<OtlpBatchImpl*>(bb);
+  if (int rc = b->arena.need(bytes)) return rc;
+  *p = b->arena.p;
+  return 0;
+}
+
+void otlp_released_set(ose_otlp_batch* bb, const ose_columns& cols, const OtlpReleasedLayout& l) {
+  auto* b = reinterpret_cast<OtlpBatchImpl*>(bb);
+  b->cols = cols;
+  b->pb = nullptr;   // the host encoder's copy is made on demand (ose_otlp_encode)
+  b->pb_len = 0;
+  b->span_ref.clear();
+  b->lay = OtlpLayout{};
+  b->layout_on_host = false;
+  b->res_on_device = true;
+  b->scopes_dev = true;
+  b->d_spans = b->d_span_ref = const_cast<uint64_t*>(l.spans);
+  b->d_span0 = const_cast<uint32_t*>(l.span0);
+  b->d_hdr = const_cast<uint64_t*>(l.hdr);
+  b->d_schema = const_cast<uint64_t*>(l.schema);
+  b->d_res_ref = const_cast<uint64_t*>(l.res_ref);
+  b->d_res_scope0 = const_cast<uint32_t*>(l.res_scope0);
+  b->d_scope_ref = const_cast<uint64_t*>(l.scope_ref);
+}
+
 // The GPU encoder for the OTLP pipeline (otlp_pipeline.cpp): *out holds the
 // batch's outputs and res_off every output's per-resource record offsets
 // (n_out x R); *gpu false when the GPU encoder declined the batch (nothing
@@ -1928,17 +1985,23 @@ const ose_columns* ose_otlp_columns(const ose_otlp_batch* bb) {
 
 int ose_otlp_timings(const ose_otlp_batch* bb, double* ms5) {
   if (!bb || !ms5) return fail(OSE_EINVAL, "NULL argument");
+  if (reinterpret_cast<const OtlpBatchImpl*>(bb)->released)
+    return fail(OSE_ENOTSUP, "ose_otlp_timings: a batch released by a groupbytrace store was not decoded");
   std::memcpy(ms5, reinterpret_cast<const OtlpBatchImpl*>(bb)->t_ms, sizeof(double) * 5);
   return 0;
 }
 
 uint32_t ose_otlp_host_spans(const ose_otlp_batch* bb) {
+  if (bb && reinterpret_cast<const OtlpBatchImpl*>(bb)->released)
+    return (uint32_t)fail(OSE_ENOTSUP, "ose_otlp_host_spans: a batch released by a groupbytrace store was not decoded");
   return bb ? reinterpret_cast<const OtlpBatchImpl*>(bb)->host_spans : 0;
 }
 
 int ose_otlp_attrset(const ose_otlp_batch* bb, uint32_t k, char* json, size_t cap) {
   if (!bb || !json) return fail(OSE_EINVAL, "NULL argument");
   const auto* b = reinterpret_cast<const OtlpBatchImpl*>(bb);
+  if (b->released)   // its res_attrset ids are the caller's stable ids (ose_gbt_add_otlp's attrset_map)
+    return fail(OSE_ENOTSUP, "ose_otlp_attrset: a released batch's attribute set ids are the caller's");
   if (k >= b->attrsets.size()) return fail(OSE_EINVAL, "attribute set index out of range");
   Json o = Json::object();
   for (auto& kv : b->attrsets[k]) o.set(kv.first, Json::str(kv.second));
@@ -2048,6 +2111,13 @@ int ose_otlp_encode(ose_engine* eng, const ose_otlp_batch* bb, const ose_outputs
   }
   d.span_size = reinterpret_cast<const uint32_t*>(h + o_size);
   if (sql) d.sql_op = h + o_sql;
+  if (b->released && !b->layout_on_host) {   // the released message buffer comes down once per release
+    const size_t len = b->cols.arena_bytes;
+    if ((rc = b->relhost.need(len + 16))) return rc;
+    if (len) HIP_TRY(hipMemcpyAsync(b->relhost.p, b->arena.p, len, hipMemcpyDeviceToHost, st));
+    b->pb = b->relhost.p;
+    b->pb_len = len;
+  }
   if ((rc = layout_to_host(b, st))) return rc;
   auto* o = new OtlpOut();
   o->e = e;
@@ -2125,6 +2195,7 @@ void ose_otlp_release(ose_otlp_batch* bb) {
   if (!bb) return;
   LastErrorScope keep("ose_otlp_release");
   auto* b = reinterpret_cast<OtlpBatchImpl*>(bb);
+  if (b->released) return;   // the store's: freed by the next release's reuse or ose_gbt_destroy
   Engine* e = b->e;
   (void)bind_device(e);
   bool pooled = false;

@@ -161,6 +161,8 @@ def lib() -> C.CDLL:
         "ose_gbt_release": (C.c_int, [_p, C.c_int64, _p, C.POINTER(C.POINTER(Columns)), C.POINTER(C.c_uint32)]),
         "ose_gbt_stats": (C.c_int, [_p, C.POINTER(C.c_uint64)]),
         "ose_gbt_download": (C.c_int, [_p, C.POINTER(Columns)]),
+        "ose_gbt_add_otlp": (C.c_int, [_p, _p, _p, C.c_int64, _p]),
+        "ose_gbt_release_otlp": (C.c_int, [_p, C.c_int64, _p, C.POINTER(_p), C.POINTER(C.c_uint32)]),
         "ose_engine_attr_key": (C.c_int, [_p, C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(C.c_uint32)]),
         "ose_engine_attr_host_rules": (C.c_uint32, [_p, C.POINTER(C.c_uint64), C.c_uint32]),
         "ose_otlp_pipeline_create": (C.c_int, [_p, _p, C.c_uint32, C.c_uint64, C.POINTER(_p)]),
@@ -197,6 +199,7 @@ def lib() -> C.CDLL:
         # host layer (odigos_amd/csrc/host.cpp)
         "osehost_last_error": (C.c_char_p, []),
         "osehost_sampling_chunks": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint32)]),
+        "osehost_gbt_copy_times": (C.c_int, [_p, C.c_int, C.POINTER(C.c_double)]),
         "osehost_stream_copy": (C.c_int, [_p, _p, C.c_size_t, C.c_int, _p, C.POINTER(C.c_double)]),
         "osehost_xgroup_create": (C.c_int, [C.c_int, C.POINTER(_p)]),
         "osehost_owner_last_general": (C.c_uint32, [_p]),
