@@ -990,4 +990,17 @@ char* osehost_router_route(const ose_router* rr, const char* attrs_json) {
   }
 }
 
+// The route table the GPU encoder reads (Router::dev_blob): up to cap bytes of
+// it into dst (NULL: none), its size, route_bits and the slots' byte count.
+int osehost_router_table(const ose_router* rr, uint8_t* dst, size_t cap, uint64_t* blob_bytes, uint32_t* route_bits,
+                         uint64_t* slots_bytes) {
+  if (!rr) return fail(OSE_EINVAL, "NULL argument");
+  const Router* r = reinterpret_cast<const Router*>(rr);
+  if (dst && cap) std::memcpy(dst, r->dev_blob.data(), std::min(cap, r->dev_blob.size()));
+  if (blob_bytes) *blob_bytes = r->dev_blob.size();
+  if (route_bits) *route_bits = r->route_bits;
+  if (slots_bytes) *slots_bytes = r->dev_slots_bytes;
+  return 0;
+}
+
 }  // extern "C"

@@ -359,6 +359,7 @@ Json traces_to_json(const Traces& t) {
       if (!ss.scope_name.empty()) sc.set("name", Json::str(ss.scope_name));
       if (!ss.scope_version.empty()) sc.set("version", Json::str(ss.scope_version));
       if (!ss.scope_attrs.kv.empty()) sc.set("attributes", attrs_to_json(ss.scope_attrs));
+      if (ss.scope_dropped) sc.set("droppedAttributesCount", Json::number(std::to_string(ss.scope_dropped)));
       sj.set("scope", std::move(sc));
       Json sps = Json::array();
       for (auto& sp : ss.spans) {

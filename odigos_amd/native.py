@@ -228,6 +228,8 @@ def lib() -> C.CDLL:
                                               C.POINTER(_p), _p]),
         "osehost_router_create_signal": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(_p)]),
         "osehost_router_route": (_p, [_p, C.c_char_p]),
+        "osehost_router_table": (C.c_int, [_p, _p, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
+                                           C.POINTER(C.c_uint64)]),
         "osehost_otlp_out_timings": (C.c_int, [_p, C.POINTER(C.c_double)]),
         "osehost_otlp_out_path": (C.c_int, [_p, C.POINTER(C.c_uint32)]),
         "osehost_parse_duration": (C.c_int, [C.c_char_p, C.POINTER(C.c_int64)]),
