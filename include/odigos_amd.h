@@ -595,6 +595,13 @@ void ose_host_free(void* p);
 int ose_otlp_decode(ose_engine* eng, const void* pb, size_t len, void* hip_stream, ose_otlp_batch** out);
 const ose_columns* ose_otlp_columns(const ose_otlp_batch* b);   /* device pointers */
 uint32_t ose_otlp_host_spans(const ose_otlp_batch* b);
+/* which path the decode took (read-only): out[0] the TracesData chain was
+ * linked on the GPU (engine option otlp_gpu_chain), [1] resources the device
+ * table missed, [2] of them keyed into the table (one Resource field or
+ * none), [3] scopes the host sized, [4] the scope redo was taken (all on the
+ * host), [5] the resource redo, [6] the span kernel (0 none, 1 LDS-staged,
+ * 2 HBM), [7] the arena was regrown for the host pass's strings */
+int ose_otlp_walk_info(const ose_otlp_batch* b, uint32_t out[8]);
 /* host wall time of the call's phases (ms): bytes in (copy / H2D issue),
  * structural walk, columns upload, span decoder (+ sync), host pass */
 int ose_otlp_timings(const ose_otlp_batch* b, double* ms5);
@@ -764,7 +771,7 @@ int ose_device_info(char* buf, size_t cap);
  * bytes after arena_bytes).  ose_otlp_encode takes it with every stage mask
  * and router it takes for a decoded batch; ose_otlp_download works;
  * ose_otlp_attrset (the ids are the caller's, through attrset_map) and
- * ose_otlp_timings return OSE_ENOTSUP, ose_otlp_host_spans
+ * ose_otlp_timings and ose_otlp_walk_info return OSE_ENOTSUP, ose_otlp_host_spans
  * (uint32_t)OSE_ENOTSUP.                                                     */
 int ose_gbt_add_otlp(ose_gbt* g, const ose_otlp_batch* b, const uint32_t* attrset_map, int64_t now_ns,
                      void* hip_stream);

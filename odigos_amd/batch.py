@@ -486,6 +486,12 @@ class DeviceView:
         return t.cpu().numpy().view(dtype)
 
 
+# ose_otlp_walk_info's words: which path a decode took
+WALK_INFO = ("gpu_chain", "res_misses", "res_keyed", "host_scopes", "scope_redo", "res_redo", "span_kernel",
+             "arena_regrown")
+SPAN_KERNEL_LDS, SPAN_KERNEL_HBM = 1, 2
+
+
 class OtlpBatch:
     """A serialized TracesData decoded on the GPU (ose_otlp_decode): device
     columns owned by the engine plus HBM outputs, usable wherever a
@@ -510,6 +516,9 @@ class OtlpBatch:
         engine.adopt(self)
         self.cols = native.Columns.from_buffer_copy(self.L.ose_otlp_columns(h).contents)
         self.host_spans = int(self.L.ose_otlp_host_spans(h))
+        wi = (C.c_uint32 * 8)()
+        native.check(self.L.ose_otlp_walk_info(h, wi))
+        self.walk_info = dict(zip(WALK_INFO, list(wi)))
         t = (C.c_double * 5)()
         native.check(self.L.ose_otlp_timings(h, t))
         self.timings_ms = dict(zip(("bytes_in", "walk", "columns", "span_kernel", "host_pass"), list(t)))

@@ -543,7 +543,7 @@ struct OtlpArgs {
   const uint8_t* key_bytes;
   uint32_t n_keys;
   uint32_t n_attr_keys;
-  uint64_t key_lens;            // bit l: some key has length l (< 64)
+  uint64_t key_lens;            // bit min(l, 63): some key has length l (a filter: the per-key compare is exact)
   uint64_t* tid;
   uint64_t* start;
   uint64_t* end;
@@ -790,7 +790,7 @@ struct OtlpFixArgs {
   uint8_t* attr_type;
   uint64_t* attr_val;
 };
-void launch_otlp_spans(const OtlpArgs& a, hipStream_t st);
+uint32_t launch_otlp_spans(const OtlpArgs& a, hipStream_t st);   // the kernel launched: 0 none, 1 LDS-staged, 2 HBM
 void launch_otlp_fix(const OtlpFixArgs& a, hipStream_t st);
 
 // odigossqldboperationprocessor's span columns from the message

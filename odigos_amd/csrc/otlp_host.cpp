@@ -189,6 +189,12 @@ struct OtlpBatchImpl {
   DevBuf arena, slab, stage, fixdev;   // device arena; device columns; pinned staging; host-pass records
   std::vector<std::vector<std::pair<std::string, std::string>>> attrsets;
   uint32_t host_spans = 0;
+  // which path the decode took (ose_otlp_walk_info): [0] the GPU chain linked,
+  // [1] resource-table misses, [2] of them entered into the table's key space
+  // (one Resource field or none), [3] scopes the host sized, [4] the scope
+  // redo, [5] the resource redo, [6] the span kernel (1 LDS-staged, 2 HBM),
+  // [7] the arena regrown
+  uint32_t walk_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   double t_ms[5] = {0, 0, 0, 0, 0};   // copy-in, walk, columns upload, span kernel (+ sync), host pass
   // for ose_otlp_encode: the caller's message and where its parts are
   const uint8_t* pb = nullptr;
@@ -278,7 +284,7 @@ OtlpEngine* otlp_engine(Engine* e, int& rc) {
     OtlpKeyDev d{(uint32_t)kv.first.size(), (uint32_t)o->key_bytes.size(), kv.second};
     o->key_bytes += kv.first;
     o->keys.push_back(d);
-    if (kv.first.size() < 64) o->key_lens |= 1ull << kv.first.size();
+    o->key_lens |= 1ull << std::min<size_t>(kv.first.size(), 63);   // bit 63: every length >= 63
   }
   const size_t kb = o->keys.size() * sizeof(OtlpKeyDev);
   std::vector<uint8_t> blob(kb + o->key_bytes.size() + 16, 0);
@@ -834,6 +840,7 @@ int res_walk_gpu(OtlpEngine* o, OtlpBatchImpl* b, const uint8_t* pb, size_t len,
     R = w.lay.res_ref.size();
   }
   *R_out = R;
+  b->walk_info[0] = gpu_chain ? 1u : 0u;
   const uint64_t RN = std::max<uint64_t>(R, 1);
   const uint32_t tiles = (uint32_t)((RN + kScanTileItems - 1) / kScanTileItems);
   struct Part { void** dst; size_t bytes; };
@@ -907,6 +914,7 @@ int res_walk_gpu(OtlpEngine* o, OtlpBatchImpl* b, const uint8_t* pb, size_t len,
   *S_out = h[2];
   // the resources the table lacks: resolved on the host
   const uint32_t nm = h[1];
+  b->walk_info[1] = nm;
   if (nm) {
     if (w.lay.res_ref.size() != R) {   // the refs the GPU chain walk wrote
       w.lay.res_ref.resize(R);
@@ -980,6 +988,7 @@ int res_walk_gpu(OtlpEngine* o, OtlpBatchImpl* b, const uint8_t* pb, size_t len,
       }
       if ((rc = t.sync(st))) return rc;
     }
+    for (uint32_t k = 0; k < nm; k++) b->walk_info[2] += keyed[k];
   }
   // the cache's attribute-set ids -> this batch's (first appearance)
   uint32_t n_sets;
@@ -1167,6 +1176,7 @@ int scope_walk_gpu(Engine* e, OtlpBatchImpl* b, Walked& w, hipStream_t st, uint6
     if (!r.ok) return fail(OSE_EINVAL, "OTLP protobuf: malformed ScopeSpans");
     patch.emplace_back(q, (uint32_t)(sizer.scope_fixed(meta) + (sch ? flen(sch) : 0)));
   }
+  b->walk_info[3] = (uint32_t)patch.size();
   for (auto& x : patch) HIP_TRY(hipMemcpyAsync(scope_size + x.first, &x.second, 4, hipMemcpyHostToDevice, st));
   if (!patch.empty()) HIP_TRY(hipStreamSynchronize(st));   // the patch sources are on this stack
   b->cols.scope_size = scope_size;
@@ -1222,6 +1232,8 @@ int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchIm
     t0 = t;
   };
   for (double& x : b->t_ms) x = 0;
+  for (int k = 0; k < 8; k++)
+    if (k != 4 && k != 5) b->walk_info[k] = 0;   // (the redo flags are the outer call's)
   // engine option otlp_sqlop: db_flags / db_query / res_sql_ok are decoded too
   const bool sql = e->has_sqlop && e->option(Engine::kOptOtlpSqlop);
   // 1. the bytes H2D (straight from the caller's buffer when it is pinned,
@@ -1254,7 +1266,10 @@ int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchIm
   if (gpu_res) {
     bool redo = false;
     if ((rc = res_walk_gpu(o, b, pb, len, st, w, &R, &S, &ra, &redo, !pinned, sql))) return rc;
-    if (redo) return decode(e, pb, len, st, b, false, true);   // a malformed record: the host walk reports it
+    if (redo) {   // a malformed record: the host walk reports it
+      b->walk_info[5] = 1;
+      return decode(e, pb, len, st, b, false, true);
+    }
   } else {
     if (!walk(o->ctx, o->res_cache, pb, len, w, gpu_scopes)) return fail(OSE_EINVAL, w.err);
     HIP_TRY(hipStreamSynchronize(st));   // the staging buffer is reused below
@@ -1279,7 +1294,10 @@ int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchIm
       if (!rc) rc = src;
     }
     if (rc) return rc;
-    if (redo) return decode(e, pb, len, st, b, true, true);   // a scope needs the host walk: all on the host
+    if (redo) {   // a scope needs the host walk: all on the host
+      b->walk_info[4] = 1;
+      return decode(e, pb, len, st, b, true, true);
+    }
     b->scopes_dev = true;
   } else {
     n = w.span_ref.size();
@@ -1420,7 +1438,7 @@ int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchIm
   (void)hipGetLastError();   // a stale error of an earlier call must not be reported as this launch's
   Engine::Timed tm{};
   e->prof_begin("otlp_span_kernel", st, tm);
-  if (n) launch_otlp_spans(a, st);
+  if (n) b->walk_info[6] = launch_otlp_spans(a, st);
   HIP_TRY(hipGetLastError());
   e->prof_end(tm, st);
   if (sql && n) {   // db_flags / db_query: a pass of its own (the span kernels stay within their register budget)
@@ -1534,6 +1552,7 @@ int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchIm
     std::swap(b->arena.p, bigger.p);
     std::swap(b->arena.cap, bigger.cap);
     c.arena = b->arena.p;
+    b->walk_info[7] = 1;
   }
   c.arena_bytes = str_base + strs.size();
   const size_t fb = up(cnt * sizeof(OtlpFix)), tb = up((size_t)cnt * K + 16), vb = up((size_t)cnt * K * 8 + 16);
@@ -1878,6 +1897,7 @@ int ose_otlp_decode(ose_engine* eng, const void* pb, size_t len, void* hip_strea
   }
   if (!b) b = new OtlpBatchImpl();
   b->e = e;
+  b->walk_info[4] = b->walk_info[5] = 0;
   const int rc = decode(e, static_cast<const uint8_t*>(pb), len, static_cast<hipStream_t>(hip_stream), b);
   if (rc) {
     (void)hipStreamSynchronize(static_cast<hipStream_t>(hip_stream));   // no copy may outlive the buffers
@@ -1995,6 +2015,14 @@ uint32_t ose_otlp_host_spans(const ose_otlp_batch* bb) {
   if (bb && reinterpret_cast<const OtlpBatchImpl*>(bb)->released)
     return (uint32_t)fail(OSE_ENOTSUP, "ose_otlp_host_spans: a batch released by a groupbytrace store was not decoded");
   return bb ? reinterpret_cast<const OtlpBatchImpl*>(bb)->host_spans : 0;
+}
+
+int ose_otlp_walk_info(const ose_otlp_batch* bb, uint32_t out[8]) {
+  if (!bb || !out) return fail(OSE_EINVAL, "NULL argument");
+  if (reinterpret_cast<const OtlpBatchImpl*>(bb)->released)
+    return fail(OSE_ENOTSUP, "ose_otlp_walk_info: a batch released by a groupbytrace store was not decoded");
+  std::memcpy(out, reinterpret_cast<const OtlpBatchImpl*>(bb)->walk_info, sizeof(uint32_t) * 8);
+  return 0;
 }
 
 int ose_otlp_attrset(const ose_otlp_batch* bb, uint32_t k, char* json, size_t cap) {

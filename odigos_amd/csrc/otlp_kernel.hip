@@ -83,7 +83,7 @@ struct KeyTab {
 };
 // the roles of key [o, o + l) (0 = not a key of interest)
 __device__ OSE_PB_INL uint64_t key_roles(const OtlpArgs& a, const KeyTab& kt, Rd& r, uint32_t o, uint32_t l) {
-  if (l >= 64 || !((a.key_lens >> l) & 1)) return 0;
+  if (!((a.key_lens >> (l < 63 ? l : 63)) & 1)) return 0;   // bit 63: every length >= 63
   uint64_t roles = 0;
   for (uint32_t k = 0; k < a.n_keys; k++) {
     const OtlpKeyDev kd = kt.keys[k];
@@ -569,7 +569,8 @@ __global__ __launch_bounds__(kOThreads) void otlp_chain_seg_kernel(OtlpChainArgs
     const uint64_t at = r.i;
     uint32_t f, wt;
     if (!r.tag(f, wt)) break;
-    const bool rec = f == 1 && wt == 2;
+    if (f == 1 && wt != 2) { r.bad = true; break; }   // resource_spans in another wire type: UnmarshalTraces rejects it
+    const bool rec = f == 1;
     if (k < kChainList) a.list[(uint64_t)t * kChainList + k] = at | ((uint64_t)rec << 63);
     k++;
     if (!r.skip(wt)) break;
@@ -769,13 +770,15 @@ void launch_otlp_scope_spans(const OtlpScopeArgs& a, hipStream_t st) {
                        dim3(kOThreads), 0, st, a);
 }
 
-void launch_otlp_spans(const OtlpArgs& a, hipStream_t st) {
+uint32_t launch_otlp_spans(const OtlpArgs& a, hipStream_t st) {
   const uint64_t blocks = std::min<uint64_t>((a.n_spans + kWave - 1) / kWave, 32768);
-  if (!blocks) return;
-  if (OSE_SPAN_STAGE && a.n_spans <= kSpanStageMax)
+  if (!blocks) return 0;
+  if (OSE_SPAN_STAGE && a.n_spans <= kSpanStageMax) {
     hipLaunchKernelGGL(otlp_span_lds_kernel, dim3((uint32_t)blocks), dim3(kWave), 0, st, a);
-  else
-    hipLaunchKernelGGL(otlp_span_kernel, dim3((uint32_t)blocks), dim3(kWave), 0, st, a);
+    return 1;
+  }
+  hipLaunchKernelGGL(otlp_span_kernel, dim3((uint32_t)blocks), dim3(kWave), 0, st, a);
+  return 2;
 }
 void launch_otlp_fix(const OtlpFixArgs& a, hipStream_t st) {
   const uint32_t blocks = (a.n + kOThreads - 1) / kOThreads;

@@ -399,24 +399,33 @@ def test_gpu_resource_walk_cold_warm_and_host():
     _, hb = _host_columns(CFG, td)
     pb = to_pb(td)
     eng = Engine(CFG)
-    for _ in range(2):
+    R = len(td["resourceSpans"])
+    for warm in (False, True):
         ob = OtlpBatch(eng, pb)
         _compare(ob.cols, hb.cols, ob.download())
+        # which path ran (ose_otlp_walk_info): cold, every row misses the device table and is keyed into
+        # it (every record here has one Resource field); warm, none misses; no silent redo either time
+        wi = ob.walk_info
+        assert (wi["res_misses"], wi["res_keyed"]) == ((0, 0) if warm else (R, R))
+        assert (wi["res_redo"], wi["scope_redo"], wi["host_scopes"], wi["gpu_chain"]) == (0, 0, 0, 0)
         ob.close()
     eng.set_option("otlp_host_resources", 1)
     ob = OtlpBatch(eng, pb)
     _compare(ob.cols, hb.cols, ob.download())
+    assert (ob.walk_info["res_misses"], ob.walk_info["res_keyed"], ob.walk_info["res_redo"]) == (0, 0, 0)
     eng.set_option("otlp_host_resources", 0)
     # a message of several copies (resources repeated, table hits in one call)
     td3 = {"resourceSpans": td["resourceSpans"] * 3}
     _, hb3 = _host_columns(CFG, td3)
     ob3 = OtlpBatch(Engine(CFG), to_pb(td3))
     _compare(ob3.cols, hb3.cols, ob3.download())
+    assert ob3.walk_info["res_misses"] == 3 * R == ob3.walk_info["res_keyed"]   # (the lookups run before any insert)
     # the TracesData chain walked on the GPU (engine option otlp_gpu_chain) equals the host's
     eng4 = Engine(CFG)
     eng4.set_option("otlp_gpu_chain", 1)
     ob4 = OtlpBatch(eng4, to_pb(td3))
     _compare(ob4.cols, hb3.cols, ob4.download())
+    assert ob4.walk_info["gpu_chain"] == 1 and ob4.walk_info["res_redo"] == 0   # linked: not the host walk's fallback
 
 
 @pytest.mark.gpu
@@ -438,6 +447,8 @@ def test_gpu_chain_walk_records_over_segments():
     eng.set_option("otlp_gpu_chain", 1)
     ob = OtlpBatch(eng, pb)
     _compare(ob.cols, hb.cols, ob.download())
+    # the GPU chain ran and its link held (it would pass silently on the host walk's fallback otherwise)
+    assert ob.walk_info["gpu_chain"] == 1 and ob.walk_info["res_redo"] == 0
     with pytest.raises(native.OseError) as ei:
         OtlpBatch(eng, pb[: len(pb) - 1000])
     assert ei.value.code == native.OSE_EINVAL
