@@ -9,6 +9,10 @@
  *   odigossqldboperationprocessor
  *                        collector/processors/odigossqldboperationprocessor
  *   odigostrafficmetrics collector/processors/odigostrafficmetrics
+ *   odigosconditionalattributes
+ *                        collector/processors/odigosconditionalattributes (the
+ *                        node collector's category-attributes profile; it has
+ *                        entry points of its own, ose_condattr_process*)
  *
  * In the reference each processor is a Go processor.Factory whose
  * processorhelper.ProcessTracesFunc walks a ptrace.Traces
@@ -136,6 +140,14 @@ extern "C" {
 /* sql_op already holds an earlier call's results: SIZE counts the attribute
  * and the longer name as if SQLOP had run in this call.  Excludes SQLOP.    */
 #define OSE_STAGE_APPLY_SQLOP  0x80u
+/* odigosconditionalattributes.  Reported in ose_engine_info.stages of an
+ * engine with the section, and never taken in a stage mask: the stage has
+ * columns and outputs of its own (ose_condattr_columns below), so every entry
+ * point with a stage mask (ose_process, ose_process_device, ose_otlp_encode,
+ * ose_otlp_pipeline_create) answers OSE_ENOTSUP and names
+ * ose_condattr_process.  The groupbytrace store and the trace-id exchange
+ * take no stage mask and do not carry the stage's columns.                  */
+#define OSE_STAGE_CONDATTR     0x100u
 
 /* ---- per-span db_flags (columnarised by the shim) --------------------
  * What odigossqldboperationprocessor/processor.go:52-61 reads from the span
@@ -777,6 +789,104 @@ int ose_gbt_add_otlp(ose_gbt* g, const ose_otlp_batch* b, const uint32_t* attrse
                      void* hip_stream);
 int ose_gbt_release_otlp(ose_gbt* g, int64_t now_ns, void* hip_stream, const ose_otlp_batch** out,
                          uint32_t* n_traces);
+
+/* ---- odigosconditionalattributes (OSE_STAGE_CONDATTR) -----------------
+ * processTraces of collector/processors/odigosconditionalattributes/
+ * processor.go:26-137 (traces only).  cfg_json section
+ * "odigosconditionalattributes": {"global_default": "...", "rules": [
+ *   {"field_to_check": "...", "field_to_check_metrics": ignored,
+ *    "new_attribute_value_configurations": {"<value>": [
+ *       {"new_attribute": "...", "value": "...", "from_field": "..."}]}}]}
+ * (config.go:7-24; there is no Validate: only type errors are OSE_EINVAL).
+ *
+ * Keys are the distinct attribute names the stage reads or writes, numbered
+ * in first-appearance order: the rules in config order; of a rule first its
+ * field_to_check (unless it is "instrumentation_scope.name"), then its values
+ * in byte order, of a value its actions in order, of an action its from_field
+ * (when value is "" and from_field is not) and then its new_attribute.
+ * Targets are the distinct new_attribute names in that same order; every
+ * target is a key.  The shim asks for them with ose_engine_condattr_key and
+ * columnarises, per key, what the three attribute maps hold.
+ *
+ * Results: per target u and span i, src[u * n_spans + i] says whether the
+ * span's attribute of that name stays as it is (OSE_CA_KEEP) or
+ * PutStr(name, value) is to be applied, with val[u * n_spans + i] the value's
+ * bytes in the batch arena (OSE_CA_ARENA) or in the engine's string table
+ * (OSE_CA_CONFIG, read with ose_engine_condattr_string).  Go appends the
+ * defaults in random map order (processor.go:132), so the order of appended
+ * attributes is no contract: the shim appends in target order.             */
+#define OSE_CA_KEEP   0
+#define OSE_CA_ARENA  1
+#define OSE_CA_CONFIG 2
+
+typedef struct ose_condattr_info {
+  uint32_t n_rules;
+  uint32_t n_keys;
+  uint32_t n_targets;
+  uint32_t string_bytes;   /* the engine's string table (ose_engine_condattr_string) */
+} ose_condattr_info;
+
+typedef struct ose_condattr_columns {
+  uint64_t n_spans;
+  uint32_t n_resources;
+  uint32_t n_scopes;
+  uint64_t arena_bytes;
+  /* string bytes; 16-byte aligned base and 16 readable bytes after
+   * arena_bytes, as ose_columns.arena                                       */
+  const uint8_t* arena;
+  const uint32_t* scope;            /* [n_spans] the span's scope */
+  const uint32_t* scope_resource;   /* [n_scopes] the scope's resource */
+  const ose_strref* scope_name;     /* [n_scopes] InstrumentationScope.Name */
+  /* Key-major lookups, entry [k * n + i] (n = n_spans, n_scopes or
+   * n_resources): has = Map.Get(key) found a value of any type (the first of
+   * a repeated key); val = its AsString in the arena (read only where has).
+   * span_kv_size = the bytes that attribute takes in the span's message
+   * (tag + length + KeyValue), read only for the keys that are targets.     */
+  const uint8_t* span_has;
+  const ose_strref* span_val;
+  const uint32_t* span_kv_size;
+  const uint8_t* scope_has;
+  const ose_strref* scope_val;
+  const uint8_t* res_has;
+  const ose_strref* res_val;
+  /* optional: the span message sizes (ose_columns.span_size); needed for
+   * span_size_out                                                           */
+  const uint32_t* span_size;
+} ose_condattr_columns;
+
+typedef struct ose_condattr_outputs {
+  uint8_t* src;              /* [n_targets * n_spans] OSE_CA_* */
+  ose_strref* val;           /* [n_targets * n_spans] */
+  /* optional: span_size[i] plus, for every target put, the new KeyValue's
+   * framed size minus span_kv_size where it replaced one.  Pass it as
+   * ose_columns.span_size to a SIZE call: odigostrafficmetrics then counts
+   * what this stage added (the node collector's order).                     */
+  uint32_t* span_size_out;
+  /* one word per scope and (rule or target), written by the scope prepass of
+   * ose_condattr_process_device and read by its span kernel:
+   * ose_condattr_scratch_words(eng, n_scopes) words of device memory.
+   * ose_condattr_process ignores it (the engine stages through its own).    */
+  uint32_t* scratch;
+  uint32_t* device_status;   /* optional, [1]; the stage never sets it */
+} ose_condattr_outputs;
+
+int ose_engine_condattr_info(const ose_engine* eng, ose_condattr_info* info);
+/* key k: its bytes (valid while the engine lives), and the target it is
+ * (OSE_NONE: the stage only reads it).                                      */
+int ose_engine_condattr_key(const ose_engine* eng, uint32_t k, const char** bytes, uint32_t* len,
+                            uint32_t* target);
+/* the engine's string table: the bytes an OSE_CA_CONFIG val points into     */
+int ose_engine_condattr_string(const ose_engine* eng, const char** bytes, uint32_t* len);
+uint64_t ose_condattr_scratch_words(const ose_engine* eng, uint32_t n_scopes);
+/* Device pointers.  Two plain launches on the caller's stream (the scope
+ * prepass, then the span kernel): no host wait, no engine workspace,
+ * capturable into a hipGraph.                                               */
+int ose_condattr_process_device(ose_engine* eng, const ose_condattr_columns* cols,
+                                const ose_condattr_outputs* outs, void* hip_stream);
+/* Host pointers.  Synchronous: the columns are staged through pinned memory
+ * the engine owns, the results copied back before it returns; no pointer is
+ * retained (cgo rules).                                                     */
+int ose_condattr_process(ose_engine* eng, const ose_condattr_columns* cols, const ose_condattr_outputs* outs);
 
 #ifdef __cplusplus
 }

@@ -236,6 +236,35 @@ class Engine:
         native.check(self.L.ose_process_device(self.h, C.byref(db.cols), C.byref(db.outs), stages, group_mode,
                                                C.byref(rnd), s))
 
+    # ---- odigosconditionalattributes (ose_condattr_*) ----
+    def condattr_info(self) -> native.CondAttrInfo:
+        i = native.CondAttrInfo()
+        native.check(self.L.ose_engine_condattr_info(self.h, C.byref(i)))
+        return i
+
+    def condattr_keys(self) -> list:
+        """[(key bytes, target index or None)] in key order."""
+        out = []
+        for k in range(self.condattr_info().n_keys):
+            p, n, t = C.c_void_p(), C.c_uint32(), C.c_uint32()
+            native.check(self.L.ose_engine_condattr_key(self.h, k, C.byref(p), C.byref(n), C.byref(t)))
+            out.append((C.string_at(p.value, n.value), None if t.value == native.OSE_NONE else t.value))
+        return out
+
+    def condattr_strings(self) -> bytes:
+        """The string table an OSE_CA_CONFIG val points into."""
+        p, n = C.c_void_p(), C.c_uint32()
+        native.check(self.L.ose_engine_condattr_string(self.h, C.byref(p), C.byref(n)))
+        return C.string_at(p.value, n.value) if n.value else b""
+
+    def condattr_process(self, cb: "CondAttrHostBatch"):
+        """ose_condattr_process on host columns (synchronous, pinned staging)."""
+        native.check(self.L.ose_condattr_process(self.h, C.byref(cb.cols), C.byref(cb.outs)))
+
+    def condattr_process_device(self, db: "CondAttrDeviceBatch", stream=None):
+        s = None if stream is None else C.c_void_p(stream)
+        native.check(self.L.ose_condattr_process_device(self.h, C.byref(db.cols), C.byref(db.outs), s))
+
     def profile(self, on: bool = True):
         native.check(self.L.ose_profile_enable(self.h, int(on)))
 
@@ -273,6 +302,72 @@ class Engine:
             self.h = None
 
     __del__ = close
+
+
+CONDATTR_COLUMNS = {   # element size, rows of the key-major ones
+    "scope": 4, "scope_resource": 4, "scope_name": 8, "span_has": 1, "span_val": 8, "span_kv_size": 4,
+    "scope_has": 1, "scope_val": 8, "res_has": 1, "res_val": 8, "span_size": 4,
+}
+
+
+class CondAttrHostBatch:
+    """ose_condattr_columns / ose_condattr_outputs over numpy arrays: `arrays`
+    maps the column names of CONDATTR_COLUMNS (and "arena", padded as the ABI
+    asks) to arrays; n_targets sizes src / val."""
+
+    def __init__(self, n_spans: int, n_resources: int, n_scopes: int, arena_bytes: int, arrays: dict, n_targets: int,
+                 sized: bool = True):
+        self.n, self.U = n_spans, n_targets
+        self.arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+        c = native.CondAttrColumns()
+        c.n_spans, c.n_resources, c.n_scopes, c.arena_bytes = n_spans, n_resources, n_scopes, arena_bytes
+        for k, v in self.arrays.items():
+            setattr(c, k, v.ctypes.data)
+        self.cols = c
+        self.src = np.full(max(1, n_targets * n_spans), 0xEE, dtype=np.uint8)
+        self.val = np.zeros((max(1, n_targets * n_spans), 2), dtype=np.uint32)
+        self.span_size_out = np.zeros(max(1, n_spans), dtype=np.uint32)
+        o = native.CondAttrOutputs()
+        o.src, o.val = self.src.ctypes.data, self.val.ctypes.data
+        if sized and "span_size" in self.arrays:
+            o.span_size_out = self.span_size_out.ctypes.data
+        self.outs = o
+
+
+class CondAttrDeviceBatch:
+    """The same columns on the device (torch tensors as the allocator), with
+    the scratch ose_condattr_process_device asks for."""
+
+    def __init__(self, engine: "Engine", hb: CondAttrHostBatch, device="cuda"):
+        import torch
+        self.n, self.U = hb.n, hb.U
+        self.t = {}
+        c = native.CondAttrColumns()
+        c.n_spans, c.n_resources, c.n_scopes, c.arena_bytes = (hb.cols.n_spans, hb.cols.n_resources, hb.cols.n_scopes,
+                                                               hb.cols.arena_bytes)
+        for k, v in hb.arrays.items():
+            raw = np.frombuffer(v.tobytes() + bytes(16), dtype=np.uint8)
+            self.t[k] = torch.from_numpy(raw.copy()).to(device)
+            setattr(c, k, self.t[k].data_ptr())
+        self.cols = c
+        words = int(engine.L.ose_condattr_scratch_words(engine.h, hb.cols.n_scopes))
+        self.o = {"src": torch.full((max(1, hb.U * hb.n),), 0xEE, dtype=torch.uint8, device=device),
+                  "val": torch.zeros(8 * max(1, hb.U * hb.n), dtype=torch.uint8, device=device),
+                  "span_size_out": torch.zeros(4 * max(1, hb.n), dtype=torch.uint8, device=device),
+                  "scratch": torch.zeros(4 * max(1, words), dtype=torch.uint8, device=device),
+                  "device_status": torch.zeros(16, dtype=torch.uint8, device=device)}
+        o = native.CondAttrOutputs()
+        o.src, o.val, o.scratch = self.o["src"].data_ptr(), self.o["val"].data_ptr(), self.o["scratch"].data_ptr()
+        o.device_status = self.o["device_status"].data_ptr()
+        if hb.outs.span_size_out:
+            o.span_size_out = self.o["span_size_out"].data_ptr()
+        self.outs = o
+
+    def results(self):
+        """(src [U*n], val [U*n, 2], span_size_out [n]) as numpy."""
+        m = max(1, self.U * self.n)
+        return (self.o["src"].cpu().numpy()[:m].copy(), self.o["val"].cpu().numpy().view(np.uint32).reshape(m, 2).copy(),
+                self.o["span_size_out"].cpu().numpy().view(np.uint32)[:max(1, self.n)].copy())
 
 
 class PinnedBatch:

@@ -230,4 +230,91 @@ void columnize_span(const ColumnizeCtx& c, const Span& sp, const std::vector<uin
   }
 }
 
+// processSpan's reads (odigosconditionalattributes/processor.go:43-126) as
+// columns: per key, Map.Get on the span, scope and resource maps (:68, :80-84)
+// and AsString of what it finds (:69, :90), plus the scope names (:36).
+void columnize_condattr(const std::vector<std::string>& keys, size_t n_targets, const Traces& t, const ProtoSizer& sizer,
+                        CondAttrHostCols& o) {
+  const size_t K = keys.size(), R = t.resource_spans.size();
+  size_t S = 0, N = 0;
+  for (auto& rs : t.resource_spans) {
+    S += rs.scope_spans.size();
+    for (auto& ss : rs.scope_spans) N += ss.spans.size();
+  }
+  std::string arena;
+  auto add = [&](const Value& v) {
+    ose_strref r{(uint32_t)arena.size(), 0};
+    if (v.type == Value::TStr) arena += v.s;
+    else arena += v.AsString();
+    r.len = (uint32_t)(arena.size() - r.off);
+    return r;
+  };
+  auto pad = [](size_t x) { return std::max<size_t>(x, 1); };   // data() never NULL
+  o.scope.assign(pad(N), 0);
+  o.scope_resource.assign(pad(S), 0);
+  o.scope_name.assign(pad(S), ose_strref{0, 0});
+  o.span_has.assign(pad(K * N), 0);
+  o.span_val.assign(pad(K * N), ose_strref{0, 0});
+  o.span_kv_size.assign(pad(K * N), 0);
+  o.scope_has.assign(pad(K * S), 0);
+  o.scope_val.assign(pad(K * S), ose_strref{0, 0});
+  o.res_has.assign(pad(K * R), 0);
+  o.res_val.assign(pad(K * R), ose_strref{0, 0});
+  size_t i = 0, si = 0;
+  for (size_t ri = 0; ri < R; ri++) {
+    const ResourceSpans& rs = t.resource_spans[ri];
+    for (size_t k = 0; k < K; k++)
+      if (const Value* v = rs.resource_attrs.Get(keys[k])) {
+        o.res_has[k * R + ri] = 1;
+        o.res_val[k * R + ri] = add(*v);
+      }
+    for (auto& ss : rs.scope_spans) {
+      o.scope_resource[si] = (uint32_t)ri;
+      o.scope_name[si] = ose_strref{(uint32_t)arena.size(), (uint32_t)ss.scope_name.size()};
+      arena += ss.scope_name;
+      for (size_t k = 0; k < K; k++)
+        if (const Value* v = ss.scope_attrs.Get(keys[k])) {
+          o.scope_has[k * S + si] = 1;
+          o.scope_val[k * S + si] = add(*v);
+        }
+      for (auto& sp : ss.spans) {
+        o.scope[i] = (uint32_t)si;
+        for (size_t k = 0; k < K; k++)
+          if (const Value* v = sp.attrs.Get(keys[k])) {
+            o.span_has[k * N + i] = 1;
+            o.span_val[k * N + i] = add(*v);
+            o.span_kv_size[k * N + i] = (uint32_t)field_len(sizer.key_value(keys[k], *v));
+          }
+        i++;
+      }
+      si++;
+    }
+  }
+  o.arena.assign((arena.size() + 15) / 16 * 16 + 16, 0);
+  if (!arena.empty()) std::memcpy(o.arena.data(), arena.data(), arena.size());
+  o.src.assign(pad(n_targets * N), 0);
+  o.val.assign(pad(n_targets * N), ose_strref{0, 0});
+  o.span_size_out.assign(pad(N), 0);
+  o.cols = ose_condattr_columns{};
+  o.cols.n_spans = N;
+  o.cols.n_resources = (uint32_t)R;
+  o.cols.n_scopes = (uint32_t)S;
+  o.cols.arena_bytes = arena.size();
+  o.cols.arena = o.arena.data();
+  o.cols.scope = o.scope.data();
+  o.cols.scope_resource = o.scope_resource.data();
+  o.cols.scope_name = o.scope_name.data();
+  o.cols.span_has = o.span_has.data();
+  o.cols.span_val = o.span_val.data();
+  o.cols.span_kv_size = o.span_kv_size.data();
+  o.cols.scope_has = o.scope_has.data();
+  o.cols.scope_val = o.scope_val.data();
+  o.cols.res_has = o.res_has.data();
+  o.cols.res_val = o.res_val.data();
+  o.outs = ose_condattr_outputs{};
+  o.outs.src = o.src.data();
+  o.outs.val = o.val.data();
+  o.outs.span_size_out = o.span_size_out.data();
+}
+
 }  // namespace ose

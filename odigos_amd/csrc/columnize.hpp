@@ -78,4 +78,19 @@ void columnize_span(const ColumnizeCtx& c, const Span& sp, const std::vector<uin
 // bit 7 of the column is reserved for the exchange's owner-side records
 inline uint8_t status_column(int32_t code) { return code >= 0 && code <= 2 ? (uint8_t)code : (uint8_t)3; }
 
+// odigosconditionalattributes: the columns of ose_condattr_columns for the
+// keys of the compiled config (condattr_host.hpp), with an arena of their own
+// (the AsString of every value the stage may read), and the result buffers.
+// span_size is left to the caller (the batch's span_size column).
+struct CondAttrHostCols {
+  std::vector<uint8_t> arena;
+  std::vector<uint32_t> scope, scope_resource, span_kv_size, span_size_out;
+  std::vector<ose_strref> scope_name, span_val, scope_val, res_val, val;
+  std::vector<uint8_t> span_has, scope_has, res_has, src;
+  ose_condattr_columns cols{};
+  ose_condattr_outputs outs{};
+};
+void columnize_condattr(const std::vector<std::string>& keys, size_t n_targets, const Traces& t, const ProtoSizer& sizer,
+                        CondAttrHostCols& out);
+
 }  // namespace ose

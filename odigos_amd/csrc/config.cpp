@@ -332,4 +332,48 @@ std::string decode_sqlop_config(const Json& j, SqlOpConfig& out) {
   return "";
 }
 
+// odigosconditionalattributes/config.go:7-24: only decode errors (the
+// package has no Validate).  field_to_check_metrics belongs to the metrics
+// signal: its type is checked, its value dropped.
+std::string decode_condattr_config(const Json& j, CondAttrConfig& out) {
+  out = CondAttrConfig{};
+  if (j.is_null()) return "";
+  if (!j.is_obj()) return "expected a map for odigosconditionalattributes config";
+  TRY(get_str(j, "global_default", out.global_default));
+  const Json* rules = j.get("rules");
+  if (!rules || rules->is_null()) return "";
+  if (!rules->is_arr()) return "'rules': source data must be an array or slice";
+  for (auto& r : rules->arr) {
+    if (r.is_null()) { out.rules.emplace_back(); continue; }
+    if (!r.is_obj()) return "'rules[]' expected a map";
+    CondAttrRule rule;
+    std::string metrics;
+    TRY(get_str(r, "field_to_check", rule.field_to_check));
+    TRY(get_str(r, "field_to_check_metrics", metrics));
+    const Json* vals = r.get("new_attribute_value_configurations");
+    if (vals && !vals->is_null()) {
+      if (!vals->is_obj()) return "'new_attribute_value_configurations' expected a map";
+      for (auto& kv : vals->obj) {
+        std::vector<CondAttrAction> acts;
+        if (!kv.second.is_null()) {
+          if (!kv.second.is_arr()) return "'new_attribute_value_configurations[" + kv.first + "]': source data must be an array or slice";
+          for (auto& a : kv.second.arr) {
+            CondAttrAction act;
+            if (!a.is_null()) {
+              if (!a.is_obj()) return "'new_attribute_value_configurations[" + kv.first + "][]' expected a map";
+              TRY(get_str(a, "value", act.value));
+              TRY(get_str(a, "from_field", act.from_field));
+              TRY(get_str(a, "new_attribute", act.new_attribute));
+            }
+            acts.push_back(std::move(act));
+          }
+        }
+        rule.values[kv.first] = std::move(acts);   // a repeated JSON key: the last one, as a Go map
+      }
+    }
+    out.rules.push_back(std::move(rule));
+  }
+  return "";
+}
+
 }  // namespace ose

@@ -7,7 +7,9 @@
 //   odigosurltemplate     odigosurltemplateprocessor/config.go:11-158
 //   odigostrafficmetrics  odigostrafficmetrics/config.go:9-29, factory.go:27-32
 //   odigossqldboperationprocessor  odigossqldboperationprocessor/config.go:7-23
+//   odigosconditionalattributes    odigosconditionalattributes/config.go:7-24
 #pragma once
+#include <map>
 #include <optional>
 #include <string>
 #include <vector>
@@ -76,12 +78,26 @@ struct SqlOpConfig {               // config.go:7-16; Validate never fails (:20-
   std::vector<std::string> exclude_language;
 };
 
+// ---------------- odigosconditionalattributes ----------------
+struct CondAttrAction {            // NewAttributeValueConfiguration (config.go:20-24)
+  std::string value, from_field, new_attribute;
+};
+struct CondAttrRule {              // ConditionalRule (config.go:14-18); field_to_check_metrics is not kept
+  std::string field_to_check;
+  std::map<std::string, std::vector<CondAttrAction>> values;   // byte order
+};
+struct CondAttrConfig {            // config.go:7-10; there is no Validate
+  std::vector<CondAttrRule> rules;
+  std::string global_default;
+};
+
 // Each decode_* returns "" on success or the error the Go code would return
 // (mapstructure decode error, then Validate()).
 std::string decode_url_config(const Json& j, UrlTemplateConfig& out);
 std::string decode_sampling_config(const Json& j, SamplingConfig& out);
 std::string decode_traffic_config(const Json& j, TrafficMetricsConfig& out);
 std::string decode_sqlop_config(const Json& j, SqlOpConfig& out);
+std::string decode_condattr_config(const Json& j, CondAttrConfig& out);
 
 // Rule-string parsing shared by Validate and the compiled tables
 // (templatize.go:97-190).

@@ -150,6 +150,7 @@ Engine::~Engine() {
   release_batch_pool(this);
   release_otlp(this);
   release_encode(this);
+  release_condattr(this);
   for (auto& t : timed) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
   for (auto s : streams) (void)hipStreamDestroy(s);
   for (auto ev : event_pool) (void)hipEventDestroy(ev);
@@ -519,6 +520,7 @@ int run_url_back(Engine* e, const UrlKernelArgs& a, hipStream_t st) {
 int run_stages(Engine* e, const ose_columns* c, const ose_outputs* o, uint32_t mask, uint32_t group_mode,
                const ose_rand* rnd, hipStream_t st) {
   if (!c || !o) return fail(OSE_EINVAL, "columns and outputs are required");
+  if (mask & OSE_STAGE_CONDATTR) return refuse_condattr("ose_process and ose_process_device");
   if (mask & ~(OSE_STAGE_SAMPLE | OSE_STAGE_TEMPLATE | OSE_STAGE_SIZE | OSE_STAGE_APPLY_KEEP | OSE_STAGE_TEMPLATE_REFS |
                OSE_STAGE_APPLY_TEMPLATE | OSE_STAGE_SQLOP | OSE_STAGE_APPLY_SQLOP))
     return fail(OSE_EINVAL, "unknown stage bit");
@@ -775,6 +777,12 @@ int ose_engine_create(const char* cfg_json, ose_engine** out) {
     if (!err.empty()) { delete e; return fail(OSE_EINVAL, err); }
     e->has_sqlop = true;
   }
+  if (const Json* j = root.get("odigosconditionalattributes")) {
+    err = decode_condattr_config(*j, e->condattr);
+    if (!err.empty()) { delete e; return fail(OSE_EINVAL, err); }
+    if (const int crc = compile_condattr(e->condattr, e->condattr_tab)) { delete e; return crc; }
+    e->has_condattr = true;
+  }
   if (e->has_url) {
     int rc = build_url_blob(e->url, e->url_blob_host, e->max_name);
     if (rc) { delete e; return rc; }
@@ -854,6 +862,10 @@ int ose_engine_create(const char* cfg_json, ose_engine** out) {
     rc = upload(st, &e->shard_tables_dev);
     if (rc) { delete e; return rc; }
   }
+  if (e->has_condattr) {
+    rc = upload(e->condattr_tab.blob, &e->condattr_blob_dev);
+    if (rc) { delete e; return rc; }
+  }
   if (!e->attr_blob_host.empty()) {
     rc = upload(e->attr_blob_host, &e->attr_blob_dev);
     if (rc) { delete e; return rc; }
@@ -931,7 +943,8 @@ int ose_engine_get_info(const ose_engine* eng, ose_engine_info* info) {
   if (!eng || !info) return fail(OSE_EINVAL, "NULL argument");
   const Engine* e = reinterpret_cast<const Engine*>(eng);
   info->stages = (e->has_sampling ? OSE_STAGE_SAMPLE : 0) | (e->has_url ? OSE_STAGE_TEMPLATE : 0) |
-                 (e->has_traffic ? OSE_STAGE_SIZE : 0) | (e->has_sqlop ? OSE_STAGE_SQLOP : 0);
+                 (e->has_traffic ? OSE_STAGE_SIZE : 0) | (e->has_sqlop ? OSE_STAGE_SQLOP : 0) |
+                 (e->has_condattr ? OSE_STAGE_CONDATTR : 0);
   info->max_template_name = e->max_name;
   info->inverse_sampling = e->inverse;
   info->traffic_sampling_ratio = e->traffic.sampling_ratio;

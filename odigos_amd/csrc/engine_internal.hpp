@@ -12,6 +12,7 @@
 
 #include "../../include/odigos_amd.h"
 #include "config.hpp"
+#include "condattr_host.hpp"
 
 namespace ose {
 
@@ -48,6 +49,7 @@ void release_batch_pool(Engine* e);                // batch.cpp
 struct OtlpEngine;
 void release_otlp(Engine* e);                      // otlp_host.cpp
 void release_encode(Engine* e);                    // otlp_encode.cpp
+void release_condattr(Engine* e);                  // condattr_host.cpp
 
 // What the groupbytrace store (gbt_host.cpp) reads of a decoded ose_otlp_batch
 // and writes into the one it releases (otlp_host.cpp owns the type).
@@ -146,6 +148,17 @@ struct Engine {
   TrafficMetricsConfig traffic;
   SqlOpConfig sqlop;
   bool has_url = false, has_sampling = false, has_traffic = false, has_sqlop = false;
+  // odigosconditionalattributes (condattr_host.cpp): the compiled config, its
+  // device copy, and the pinned and device staging of ose_condattr_process
+  // (one call at a time: condattr_mu)
+  CondAttrConfig condattr;
+  bool has_condattr = false;
+  CondAttrCompiled condattr_tab;
+  uint8_t* condattr_blob_dev = nullptr;
+  std::mutex condattr_mu;
+  void* condattr_pin = nullptr;
+  void* condattr_stage = nullptr;
+  size_t condattr_pin_cap = 0, condattr_stage_cap = 0;
   // ose_engine_set_option: alternative implementations of the OTLP legs
   // (the default path is the fast one; these select the others, for tests
   // that compare the two)
@@ -269,6 +282,9 @@ size_t size_scratch_bytes(uint64_t n_scopes, uint64_t n_resources);
 int run_sqlop(Engine* e, const ose_columns* c, const ose_outputs* o, hipStream_t st);
 int check_sqlop_size(const ose_columns* c, const ose_outputs* o);
 int run_sqlop_size_tail(Engine* e, const SizeKernelArgs& a, const uint8_t* sql_op, hipStream_t st);
+// odigosconditionalattributes has entry points of its own: the answer of
+// every entry point that takes a stage mask holding OSE_STAGE_CONDATTR
+int refuse_condattr(const char* entry);
 // every rule chunk's endpoint bits of the spans as planes of n words (a
 // config with spilled route bytes: Engine::sampling_spill), sampling_host.cpp
 int spill_endpoint_planes(Engine* e, const ose_columns* c, Workspace* ws, hipStream_t st, const uint64_t** out);

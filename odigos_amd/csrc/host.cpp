@@ -82,7 +82,7 @@ void HostBatch::bind() {
 namespace {
 
 const char* kProcType[] = {"odigossampling", "odigosurltemplate", "odigostrafficmetrics", "pipeline",
-                           "odigossqldboperationprocessor"};
+                           "odigossqldboperationprocessor", "odigosconditionalattributes"};
 // processor.go:19-27, indexed by OSE_SQLOP_*
 const char* kSqlOpName[] = {"", "SELECT", "INSERT", "UPDATE", "DELETE", "CREATE", "DROP", "ALTER"};
 
@@ -99,10 +99,21 @@ TracesProcessor::TracesProcessor(ProcKind k, const Json& cfg) : kind_(k), cfg_js
       if (err_.empty()) if (const Json* j = c.get("odigosurltemplate")) { err_ = decode_url_config(*j, url_); has_url_ = true; }
       if (err_.empty()) if (const Json* j = c.get("odigostrafficmetrics")) { err_ = decode_traffic_config(*j, traffic_); has_traffic_ = true; }
       if (err_.empty()) if (const Json* j = c.get("odigossqldboperationprocessor")) { err_ = decode_sqlop_config(*j, sqlop_); has_sqlop_ = true; }
+      if (err_.empty()) if (const Json* j = c.get("odigosconditionalattributes")) {
+        err_ = decode_condattr_config(*j, condattr_);
+        has_condattr_ = true;
+        // the reference orders it before odigostrafficmetrics on the node
+        // collector and nowhere else
+        if (err_.empty() && (has_sampling_ || has_url_ || has_sqlop_))
+          err_ = "not supported (OSE_ENOTSUP): odigosconditionalattributes runs in a pipeline with odigostrafficmetrics only; "
+                 "the reference defines no order against odigossampling, odigosurltemplate and odigossqldboperationprocessor";
+      }
       group_mode = OSE_GROUP_TRACE_ID;
       break;
     case ProcKind::SqlOp: err_ = decode_sqlop_config(c, sqlop_); has_sqlop_ = true; break;
+    case ProcKind::CondAttr: err_ = decode_condattr_config(c, condattr_); has_condattr_ = true; break;
   }
+  if (err_.empty() && has_condattr_ && compile_condattr(condattr_, condattr_tab_)) err_ = ose_last_error();
   // span_attribute conditions: compiled here (json ones run in the walk);
   // newUrlTemplateProcessor's errors are decode_url_config's (factory.go:37-40)
   if (err_.empty())
@@ -116,7 +127,7 @@ TracesProcessor::~TracesProcessor() {
 
 uint32_t TracesProcessor::stages() const {
   return (has_sampling_ ? OSE_STAGE_SAMPLE : 0) | (has_url_ ? OSE_STAGE_TEMPLATE : 0) | (has_traffic_ ? OSE_STAGE_SIZE : 0) |
-         (has_sqlop_ ? OSE_STAGE_SQLOP : 0);
+         (has_sqlop_ ? OSE_STAGE_SQLOP : 0) | (has_condattr_ ? OSE_STAGE_CONDATTR : 0);
 }
 
 int TracesProcessor::ensure_engine() {   // callers hold mu_
@@ -364,6 +375,11 @@ std::unique_ptr<HostBatch> TracesProcessor::Columnarize(const Traces& td, bool k
   if (hb->path.empty()) hb->path.push_back(ose_strref{0, 0});
   if (hb->route.empty()) hb->route.push_back(ose_strref{0, 0});
   hb->bind();
+  if (has_condattr_) {
+    hb->ca = std::make_unique<CondAttrHostCols>();
+    columnize_condattr(condattr_tab_.keys, condattr_tab_.target_key.size(), t, ProtoSizer{}, *hb->ca);
+    hb->ca->cols.span_size = hb->span_size.data();
+  }
   return hb;
 }
 
@@ -468,6 +484,20 @@ void TracesProcessor::Apply(HostBatch& hb, Traces& td) {
             std::swap(sp.name, nm);
             old.strs.push_back(std::move(nm));
           }
+          // odigosconditionalattributes (processor.go:81-94, :114, :120, :134):
+          // PutStr of every target the stage put, in target order
+          if (kept && (st & OSE_STAGE_CONDATTR) && hb.ca) {
+            const CondAttrHostCols& ca = *hb.ca;
+            const size_t U = condattr_tab_.target_key.size();
+            for (size_t u = 0; u < U; u++) {
+              const uint8_t src = ca.src[u * N + i];
+              if (src == OSE_CA_KEEP) continue;
+              const ose_strref r = ca.val[u * N + i];
+              const uint8_t* base = src == OSE_CA_CONFIG ? condattr_tab_.blob.data() + condattr_tab_.strings_off : ca.arena.data();
+              put_str(old, sp.attrs, condattr_tab_.keys[condattr_tab_.target_key[u]],
+                      std::string_view(reinterpret_cast<const char*>(base) + r.off, r.len));
+            }
+          }
           if (by_trace && kept) {   // RemoveIf, keeping order
             if (w != q) std::swap(ss.spans[w], sp);
             w++;
@@ -550,6 +580,20 @@ int TracesProcessor::ProcessTraces(Traces& td, double* phase_s) {
   }
   auto hb = Columnarize(td);
   lap(0);
+  // odigosconditionalattributes first: odigostrafficmetrics then sizes the
+  // spans with what it added (span_size_out in place of span_size)
+  if (has_condattr_) {
+    rc = ose_condattr_process(eng_, &hb->ca->cols, &hb->ca->outs);
+    if (rc) return rc;
+    if (has_traffic_ && hb->cols.n_spans)
+      std::memcpy(hb->span_size.data(), hb->ca->span_size_out.data(), 4 * (size_t)hb->cols.n_spans);
+    if (!(stages() & ~OSE_STAGE_CONDATTR)) {
+      lap(2);
+      Apply(*hb, td);
+      lap(4);
+      return 0;
+    }
+  }
   ose_columns dims = hb->cols;
   ose_batch* b = nullptr;
   rc = ose_batch_acquire(eng_, &dims, &b);
@@ -601,7 +645,7 @@ int TracesProcessor::ProcessTraces(Traces& td, double* phase_s) {
   std::memset(o->attrset_bytes, 0, 8 * (size_t)A);
   std::memset(o->accepted_spans, 0, 8);
   lap(1);
-  rc = ose_process(eng_, b, stages(), group_mode, &rnd);
+  rc = ose_process(eng_, b, stages() & ~OSE_STAGE_CONDATTR, group_mode, &rnd);
   if (rc) { ose_batch_release(b); return rc; }
   lap(2);
   // read back into the host batch and apply
@@ -679,6 +723,7 @@ void* osehost_processor_create(const char* type, const char* cfg_json) {
   else if (t == "odigostrafficmetrics") k = ProcKind::TrafficMetrics;
   else if (t == "pipeline") k = ProcKind::Pipeline;
   else if (t == "odigossqldboperationprocessor") k = ProcKind::SqlOp;
+  else if (t == "odigosconditionalattributes") k = ProcKind::CondAttr;
   else { g_host_err = "unknown processor type: " + t; return nullptr; }
   Json cfg;
   try {
@@ -729,6 +774,16 @@ void* osehost_columnarize(void* p, const char* traces_json) {
 }
 ose_columns* osehost_batch_columns(void* hb) { return &static_cast<HostBatch*>(hb)->cols; }
 ose_outputs* osehost_batch_outputs(void* hb) { return &static_cast<HostBatch*>(hb)->outs; }
+// odigosconditionalattributes' columns and results of the batch (NULL for a
+// processor without the section)
+ose_condattr_columns* osehost_batch_condattr_columns(void* hb) {
+  auto* b = static_cast<HostBatch*>(hb);
+  return b->ca ? &b->ca->cols : nullptr;
+}
+ose_condattr_outputs* osehost_batch_condattr_outputs(void* hb) {
+  auto* b = static_cast<HostBatch*>(hb);
+  return b->ca ? &b->ca->outs : nullptr;
+}
 int osehost_apply(void* p, void* hb, char** out) {
   auto* tp = static_cast<TracesProcessor*>(p);
   auto* b = static_cast<HostBatch*>(hb);

@@ -4,7 +4,8 @@
 //   NewFactory()                     odigossamplingprocessor/factory.go:13-19,
 //                                    odigosurltemplateprocessor/factory.go:19-25,
 //                                    odigostrafficmetrics/factory.go:18-26,
-//                                    odigossqldboperationprocessor/factory.go
+//                                    odigossqldboperationprocessor/factory.go,
+//                                    odigosconditionalattributes/factory.go:13-20
 //   Factory::CreateDefaultConfig()   sampling factory.go:21-27 (empty rule lists),
 //                                    urltemplate factory.go:27-29 (&Config{}),
 //                                    trafficmetrics factory.go:28-32 (SamplingRatio 1.0)
@@ -22,6 +23,7 @@
 #include "config.hpp"
 #include "pdata.hpp"
 #include "columnize.hpp"
+#include "condattr_host.hpp"
 #include "span_attr.hpp"
 
 namespace ose {
@@ -45,6 +47,8 @@ struct HostBatch {
   bool has_sqlop = false;
   std::vector<uint8_t> db_flags, res_sql_ok, sql_op;
   std::vector<ose_strref> db_query;
+  // odigosconditionalattributes: its columns and results (NULL otherwise)
+  std::unique_ptr<CondAttrHostCols> ca;
   // outputs
   std::vector<uint8_t> keep, trace_keep, trace_level, url_out, tmpl_arena;
   std::vector<uint32_t> trace_count, trace_first_span, device_status;
@@ -56,7 +60,7 @@ struct HostBatch {
   void bind();   // point cols/outs at the vectors
 };
 
-enum class ProcKind { Sampling, UrlTemplate, TrafficMetrics, Pipeline, SqlOp };
+enum class ProcKind { Sampling, UrlTemplate, TrafficMetrics, Pipeline, SqlOp, CondAttr };
 
 struct Counter {   // one otel Int64Counter data point
   std::vector<std::pair<std::string, std::string>> attrs;
@@ -92,6 +96,11 @@ class TracesProcessor {
   TrafficMetricsConfig traffic_;
   SqlOpConfig sqlop_;
   bool has_url_ = false, has_sampling_ = false, has_traffic_ = false, has_sqlop_ = false;
+  // odigosconditionalattributes: runs before odigostrafficmetrics (the node
+  // collector's order), through ose_condattr_process
+  CondAttrConfig condattr_;
+  CondAttrCompiled condattr_tab_;
+  bool has_condattr_ = false;
   ColumnizeCtx ctx_;   // the walk's view of the config (columnize.hpp)
   ose_engine* eng_ = nullptr;
   uint64_t seed_ = 0x0D16A5EEDull;

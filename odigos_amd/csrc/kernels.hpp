@@ -500,6 +500,18 @@ struct SqlSizeArgs {
 };
 void launch_sqlop_size_spans(const SqlSizeArgs& a, hipStream_t st);
 
+// odigosconditionalattributes (condattr_kernel.hip): the scope prepass (one
+// lane per scope, fills scratch) and the span kernel (one lane per span,
+// grid-stride), both running the steps of condattr_device.hpp over the
+// compiled config blob.
+struct CondAttrArgs {
+  const uint8_t* blob;
+  ose_condattr_columns c;
+  ose_condattr_outputs o;
+};
+void launch_condattr_scopes(const CondAttrArgs& a, hipStream_t st);
+void launch_condattr_spans(const CondAttrArgs& a, hipStream_t st);
+
 // span_attribute conditions (attr_kernel.hip): out[i] = host_bits[i] &
 // host_mask | the bits of the GPU-evaluated rules the span meets.
 struct AttrArgs {

@@ -2047,6 +2047,7 @@ int encode_threads() { return parallel_width(); }
 int ose_otlp_encode(ose_engine* eng, const ose_otlp_batch* bb, const ose_outputs* outs, uint32_t stages,
                     uint32_t group_mode, const ose_router* router, void* hip_stream, ose_otlp_out** out) {
   if (!eng || !bb || !out) return fail(OSE_EINVAL, "NULL argument");
+  if (stages & OSE_STAGE_CONDATTR) return refuse_condattr("ose_otlp_encode");
   Engine* e = reinterpret_cast<Engine*>(eng);
   // odigossqldboperationprocessor's attribute and name are written only under
   // the engine option otlp_sqlop (the default until the next ABI version: refused)

@@ -488,6 +488,7 @@ int ose_otlp_pipeline_create(ose_engine* eng, const ose_router* router, uint32_t
                              ose_otlp_pipeline** out) {
   if (!eng || !out) return fail(OSE_EINVAL, "NULL argument");
   *out = nullptr;
+  if (stages & OSE_STAGE_CONDATTR) return refuse_condattr("ose_otlp_pipeline_create");
   Engine* e = reinterpret_cast<Engine*>(eng);
   // odigossqldboperationprocessor rides the OTLP path only under the engine
   // option otlp_sqlop, as set when the pipeline is created

@@ -2,8 +2,10 @@
 
 ``Processor(type, cfg)`` mirrors ``NewFactory().CreateTraces(...)`` of the
 reference's ``odigossampling`` / ``odigosurltemplate`` /
-``odigostrafficmetrics`` / ``odigossqldboperationprocessor`` (plus ``pipeline``:
-the configured ones in gateway order), and
+``odigostrafficmetrics`` / ``odigossqldboperationprocessor`` /
+``odigosconditionalattributes`` (plus ``pipeline``: the configured ones in
+gateway order, or odigosconditionalattributes before odigostrafficmetrics, the
+node collector's order), and
 ``consume`` mirrors ``ProcessTracesFunc`` on OTLP/JSON traces.
 """
 from __future__ import annotations
@@ -15,7 +17,7 @@ from typing import Any
 from . import native
 
 PROCESSOR_TYPES = ("odigossampling", "odigosurltemplate", "odigostrafficmetrics", "pipeline",
-                   "odigossqldboperationprocessor")
+                   "odigossqldboperationprocessor", "odigosconditionalattributes")
 
 
 def _enc_str(s) -> str:
@@ -156,6 +158,9 @@ class HostBatch:
         self.proc, self.h, self.L = proc, h, proc.L
         self.cols = self.L.osehost_batch_columns(h).contents
         self.outs = self.L.osehost_batch_outputs(h).contents
+        ca = self.L.osehost_batch_condattr_columns(h)   # odigosconditionalattributes' columns, or None
+        self.condattr_cols = ca.contents if ca else None
+        self.condattr_outs = self.L.osehost_batch_condattr_outputs(h).contents if ca else None
 
     def apply(self) -> dict:
         out = C.c_void_p()

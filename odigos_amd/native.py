@@ -53,6 +53,9 @@ STAGE_TEMPLATE_REFS = 0x10
 STAGE_APPLY_TEMPLATE = 0x20
 STAGE_SQLOP = 0x40
 STAGE_APPLY_SQLOP = 0x80
+STAGE_CONDATTR = 0x100
+# ose_condattr_outputs.src (odigosconditionalattributes)
+CA_KEEP, CA_ARENA, CA_CONFIG = range(3)
 XREC_BYTES = 56
 
 GROUP_TRACE_ID = 0
@@ -98,6 +101,20 @@ class Outputs(C.Structure):
         ("device_status", _p),
         ("sql_op", _p),
     ]
+
+
+class CondAttrInfo(C.Structure):
+    _fields_ = [("n_rules", C.c_uint32), ("n_keys", C.c_uint32), ("n_targets", C.c_uint32), ("string_bytes", C.c_uint32)]
+
+
+class CondAttrColumns(C.Structure):
+    _fields_ = [("n_spans", C.c_uint64), ("n_resources", C.c_uint32), ("n_scopes", C.c_uint32), ("arena_bytes", C.c_uint64)] + [
+        (f, _p) for f in ("arena", "scope", "scope_resource", "scope_name", "span_has", "span_val", "span_kv_size",
+                          "scope_has", "scope_val", "res_has", "res_val", "span_size")]
+
+
+class CondAttrOutputs(C.Structure):
+    _fields_ = [(f, _p) for f in ("src", "val", "span_size_out", "scratch", "device_status")]
 
 
 class EngineInfo(C.Structure):
@@ -195,6 +212,12 @@ def lib() -> C.CDLL:
         "ose_exchange_sample": (C.c_int, [_p, C.POINTER(Columns), C.POINTER(Outputs), _p, C.c_int, C.c_int,
                                           C.POINTER(Rand), _p, _p]),
         "ose_allreduce_counters": (C.c_int, [_p, _p, C.c_uint64, _p, _p]),
+        "ose_engine_condattr_info": (C.c_int, [_p, C.POINTER(CondAttrInfo)]),
+        "ose_engine_condattr_key": (C.c_int, [_p, C.c_uint32, C.POINTER(_p), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "ose_engine_condattr_string": (C.c_int, [_p, C.POINTER(_p), C.POINTER(C.c_uint32)]),
+        "ose_condattr_scratch_words": (C.c_uint64, [_p, C.c_uint32]),
+        "ose_condattr_process_device": (C.c_int, [_p, C.POINTER(CondAttrColumns), C.POINTER(CondAttrOutputs), _p]),
+        "ose_condattr_process": (C.c_int, [_p, C.POINTER(CondAttrColumns), C.POINTER(CondAttrOutputs)]),
         "ose_profile_enable": (C.c_int, [_p, C.c_int]),
         "ose_profile_read": (C.c_int, [_p, C.c_char_p, C.c_size_t]),
         # host layer (odigos_amd/csrc/host.cpp)
@@ -242,6 +265,11 @@ def lib() -> C.CDLL:
                                                C.POINTER(C.c_int)]),
         "osehost_span_attr_eval": (C.c_int, [C.c_char_p, C.c_char_p]),
         "osehost_sqlop_detect": (C.c_uint32, [C.c_char_p, C.c_size_t]),
+        "osehost_condattr_compile": (C.c_int, [C.c_char_p, C.POINTER(CondAttrInfo), C.POINTER(_p)]),
+        "osehost_condattr_blob": (C.c_int, [C.c_char_p, C.POINTER(_p), C.POINTER(C.c_size_t)]),
+        "osehost_condattr_span": (C.c_int, [C.c_char_p, C.POINTER(CondAttrColumns), C.POINTER(CondAttrOutputs)]),
+        "osehost_batch_condattr_columns": (C.POINTER(CondAttrColumns), [_p]),
+        "osehost_batch_condattr_outputs": (C.POINTER(CondAttrOutputs), [_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
