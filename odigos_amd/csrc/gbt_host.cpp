@@ -970,6 +970,23 @@ int osehost_gbt_copy_times(ose_gbt* gg, int on, double* ms2) {
   return 0;
 }
 
+// Test seam (tests/gbt_layouts.py): the host's bookkeeping, so that a layout
+// proves the growth, the rebuild or the wrap it was laid for.  Reads host
+// fields only: nothing is launched, nothing changes.  out[0, min(n, 13)):
+// table_slots, epoch, slots_used, pool_begin, pool_end, scope_begin,
+// scope_end, arena_begin, arena_end, next_seq, rel_end, epochs, n_attrsets.
+// Returns the number of fields there are.
+int osehost_gbt_state(const ose_gbt* gg, uint64_t* out, uint32_t n) {
+  if (!gg || !out) return fail(OSE_EINVAL, "NULL argument");
+  const auto* g = reinterpret_cast<const Gbt*>(gg);
+  const uint64_t v[] = {g->table_slots, g->epoch,       g->slots_used, g->pool_begin, g->pool_end,
+                        g->scope_begin, g->scope_end,   g->arena_begin, g->arena_end, g->next_seq,
+                        g->rel_end,     g->epochs.size(), g->n_attrsets};
+  const uint32_t have = (uint32_t)(sizeof(v) / sizeof(v[0]));
+  for (uint32_t k = 0; k < std::min(n, have); k++) out[k] = v[k];
+  return (int)have;
+}
+
 // Test seam (CPU): Go's time.ParseDuration as the store reads wait_duration
 int osehost_parse_duration(const char* s, int64_t* out) {
   if (!s || !out) return fail(OSE_EINVAL, "NULL argument");

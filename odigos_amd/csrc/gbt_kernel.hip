@@ -290,6 +290,13 @@ __global__ __launch_bounds__(kGbtThreads) void gbt_assign_kernel(GbtArgs a) {
   if (i >= a.n || !a.flag[i]) return;
   const uint64_t seq = a.next_seq + a.rank[i];
   a.table[a.slot_of[i]].seq = seq;
+  // The ring slot belongs to the newest trace that maps to it.  An add that
+  // creates more than ring_n traces (totals[0] of them) has several creators
+  // per slot, and two 8-byte stores from unordered lanes: only the last of
+  // them writes (the others' traces are evicted by it anyway), so the rebuild
+  // re-inserts the live traces under their own ids.  With W > 1 ring_n is
+  // pool_cap and created <= n <= pool_cap: every creator writes.
+  if ((uint64_t)a.rank[i] + a.ring_n < a.totals[0]) return;
   const uint64_t r = seq % a.ring_n;
   a.ring_tid[2 * r] = a.cols.trace_id[2 * i];
   a.ring_tid[2 * r + 1] = a.cols.trace_id[2 * i + 1];

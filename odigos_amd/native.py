@@ -224,6 +224,7 @@ def lib() -> C.CDLL:
         "osehost_last_error": (C.c_char_p, []),
         "osehost_sampling_chunks": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint32)]),
         "osehost_gbt_copy_times": (C.c_int, [_p, C.c_int, C.POINTER(C.c_double)]),
+        "osehost_gbt_state": (C.c_int, [_p, C.POINTER(C.c_uint64), C.c_uint32]),
         "osehost_stream_copy": (C.c_int, [_p, _p, C.c_size_t, C.c_int, _p, C.POINTER(C.c_double)]),
         "osehost_xgroup_create": (C.c_int, [C.c_int, C.POINTER(_p)]),
         "osehost_owner_last_general": (C.c_uint32, [_p]),
