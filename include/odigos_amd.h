@@ -145,7 +145,10 @@ extern "C" {
  * columns and outputs of its own (ose_condattr_columns below), so every entry
  * point with a stage mask (ose_process, ose_process_device, ose_otlp_encode,
  * ose_otlp_pipeline_create) answers OSE_ENOTSUP and names
- * ose_condattr_process.  The groupbytrace store and the trace-id exchange
+ * ose_condattr_process.  (On the OTLP path the stage's columns come from
+ * ose_otlp_decode and its results go to ose_otlp_encode_condattr, under the
+ * engine option "otlp_condattr"; the stage itself still runs through
+ * ose_condattr_process_device.)  The groupbytrace store and the trace-id exchange
  * take no stage mask and do not carry the stage's columns.                  */
 #define OSE_STAGE_CONDATTR     0x100u
 
@@ -418,7 +421,7 @@ int ose_engine_attr_key(const ose_engine* eng, uint32_t k, const char** key, uin
  *   "otlp_host_resources"  ResourceSpans on the host, ScopeSpans on the GPU
  *   "otlp_host_scopes"     ResourceSpans and ScopeSpans on the host
  *   "encode_host"          ose_otlp_encode always uses the host encoder
- * and one feature switch:
+ * and two feature switches:
  *   "otlp_sqlop"           the OTLP path carries odigossqldboperationprocessor:
  *                          ose_otlp_decode fills db_flags / db_query /
  *                          res_sql_ok, ose_otlp_encode applies sql_op, and
@@ -428,6 +431,15 @@ int ose_engine_attr_key(const ose_engine* eng, uint32_t k, const char** key, uin
  *                          without the odigossqldboperationprocessor section.
  *                          Off by default; on by default from the next ABI
  *                          version.
+ *   "otlp_condattr"        the OTLP path carries odigosconditionalattributes:
+ *                          ose_otlp_decode also makes the stage's columns
+ *                          (ose_otlp_condattr_columns) and
+ *                          ose_otlp_encode_condattr writes the stage's puts.
+ *                          It applies to decodes and encodes after it is set.
+ *                          OSE_EINVAL on an engine without the
+ *                          odigosconditionalattributes section.  Off by
+ *                          default: every entry point then answers as before
+ *                          and no column of the stage is allocated.
  * and one witness for tests:
  *   "url_path_counts"      every TEMPLATE call queues two 4-byte device copies
  *                          behind url_emit_slow_kernel, which keep the call's
@@ -887,6 +899,48 @@ int ose_condattr_process_device(ose_engine* eng, const ose_condattr_columns* col
  * the engine owns, the results copied back before it returns; no pointer is
  * retained (cgo rules).                                                     */
 int ose_condattr_process(ose_engine* eng, const ose_condattr_columns* cols, const ose_condattr_outputs* outs);
+
+/* odigosconditionalattributes on the OTLP path (engine option "otlp_condattr"):
+ * ose_otlp_decode -> ose_condattr_process_device on ose_otlp_condattr_columns(b)
+ * -> (ose_process_device(OSE_STAGE_SIZE) with span_size = span_size_out) ->
+ * ose_otlp_encode_condattr, no pdata in between: the node collector's
+ * pipeline.  The output is byte for byte what pdata marshals after the
+ * processor, appended attributes in target order.
+ *
+ * ose_otlp_condattr_columns: the stage's columns of a batch decoded with the
+ * option on (device pointers, valid as long as the batch); NULL when the
+ * option was off at the decode and for a batch owned by a groupbytrace store.
+ * arena / arena_bytes are the batch's arena, the buffer
+ * ose_otlp_columns(b)->arena names: the message bytes, then the host pass's
+ * strings (the AsString of values that are not strings, the scope names and
+ * the scopes' and resources' values).  scope, scope_resource, span_size and
+ * the three counts are the batch's own columns, shared.  A span whose value
+ * for one of the engine's keys is not a string_value takes the decoder's host
+ * pass and counts in ose_otlp_host_spans.  ose_otlp_download does not cover
+ * these columns; ose_otlp_condattr_download copies every column whose dst
+ * pointer is non-NULL (host or device memory; OSE_EINVAL where
+ * ose_otlp_condattr_columns is NULL).                                       */
+const ose_condattr_columns* ose_otlp_condattr_columns(const ose_otlp_batch* b);
+int ose_otlp_condattr_download(const ose_otlp_batch* b, const ose_condattr_columns* dst);
+/* Routes and returns outputs exactly as ose_otlp_encode with stages == 0
+ * (every span kept, no template, no SQL) and in addition, in target order,
+ * gives every span with ca->src[u * n_spans + i] != OSE_CA_KEEP
+ * PutStr(target u, value): the first KeyValue with that key is replaced where
+ * it stands, its value becoming AnyValue{string_value} (an empty string is
+ * still written); otherwise a new KeyValue goes after the span's last
+ * attribute, before the first field above 9.  OSE_CA_ARENA values are read
+ * from the batch arena, OSE_CA_CONFIG values from the engine's string table.
+ * ca->src and ca->val are device or host memory, read on hip_stream; the
+ * other members of ca are not read (the new span lengths are computed here).
+ * OSE_ENOTSUP with the option off; OSE_EINVAL for a batch decoded with the
+ * option off or owned by a groupbytrace store, a NULL src or val, or a src
+ * value above OSE_CA_CONFIG; OSE_ERANGE for an OSE_CA_ARENA ref past
+ * arena_bytes or an OSE_CA_CONFIG ref past the string table (nothing is read
+ * or written past any buffer).  The GPU encoder takes configs of up to 24
+ * targets and spans already in pdata's encoding; anything else is written by
+ * the host encoder, to the same bytes.                                       */
+int ose_otlp_encode_condattr(ose_engine* eng, const ose_otlp_batch* b, const ose_condattr_outputs* ca,
+                             const ose_router* router, void* hip_stream, ose_otlp_out** out);
 
 #ifdef __cplusplus
 }

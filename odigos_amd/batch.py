@@ -73,6 +73,9 @@ class Generator:
             L.osegen_otlp.argtypes = [C.POINTER(native.Columns), C.c_int, C.POINTER(C.c_uint64)]
             L.osegen_otlp_sql.restype = C.c_void_p
             L.osegen_otlp_sql.argtypes = [C.POINTER(native.Columns), C.c_int, C.POINTER(C.c_uint64), C.c_uint32]
+            L.osegen_otlp_scoped.restype = C.c_void_p
+            L.osegen_otlp_scoped.argtypes = [C.POINTER(native.Columns), C.c_int, C.POINTER(C.c_uint64), C.c_uint32,
+                                             C.c_char_p, C.c_void_p, C.c_uint32]
             L.osegen_otlp_free.argtypes = [C.c_void_p]
             Generator._L = L
         if world is None:
@@ -92,11 +95,18 @@ class Generator:
             n = (n + 15) // 16 * 16 + 16
         return host_array(getattr(self.cols, field), n)
 
-    def otlp(self, threads: int = 8, sql_every: int = 0) -> bytes:
+    def otlp(self, threads: int = 8, sql_every: int = 0, scope_names=None) -> bytes:
         """The batch as a serialized OTLP TracesData (gen_otlp.cpp); sql_every:
-        one span in that many also carries a db.query.text (0: none)."""
+        one span in that many also carries a db.query.text (0: none);
+        scope_names: every resource's scope name is drawn from this list."""
         n = C.c_uint64()
-        p = Generator._L.osegen_otlp_sql(C.byref(self.cols), threads, C.byref(n), sql_every)
+        if scope_names:
+            bs = [s.encode() for s in scope_names]
+            lens = np.array([len(b) for b in bs], dtype=np.uint32)
+            p = Generator._L.osegen_otlp_scoped(C.byref(self.cols), threads, C.byref(n), sql_every, b"".join(bs),
+                                                lens.ctypes.data, len(bs))
+        else:
+            p = Generator._L.osegen_otlp_sql(C.byref(self.cols), threads, C.byref(n), sql_every)
         try:   # (string_at takes an int size: messages above 2 GiB need the array view)
             return C.cast(p, C.POINTER(C.c_char * n.value)).contents.raw
         finally:
@@ -264,6 +274,17 @@ class Engine:
     def condattr_process_device(self, db: "CondAttrDeviceBatch", stream=None):
         s = None if stream is None else C.c_void_p(stream)
         native.check(self.L.ose_condattr_process_device(self.h, C.byref(db.cols), C.byref(db.outs), s))
+
+    def otlp_encode_condattr(self, batch: "OtlpBatch", outs: native.CondAttrOutputs, router: "Router | None" = None,
+                             stream=None, copy: bool = True, path: dict | None = None) -> list:
+        """ose_otlp_encode_condattr (engine option otlp_condattr): the batch
+        written out with the puts of outs.src / outs.val (device or host
+        memory), routed as OtlpBatch.encode(0) routes; `path` as take_otlp_out."""
+        h = C.c_void_p()
+        s = None if stream is None else C.c_void_p(stream)
+        native.check(self.L.ose_otlp_encode_condattr(self.h, batch.h, C.byref(outs), router.h if router is not None else None,
+                                                     s, C.byref(h)))
+        return take_otlp_out(self.L, h, copy, None, path)
 
     def profile(self, on: bool = True):
         native.check(self.L.ose_profile_enable(self.h, int(on)))
@@ -618,6 +639,30 @@ class OtlpBatch:
         native.check(self.L.ose_otlp_timings(h, t))
         self.timings_ms = dict(zip(("bytes_in", "walk", "columns", "span_kernel", "host_pass"), list(t)))
         self.outs, self.o = outputs if outputs is not None else device_outputs(self.cols, tmpl_cap=tmpl_cap)
+        # odigosconditionalattributes' columns (device pointers; None unless the
+        # engine option otlp_condattr was on at the decode)
+        p = self.L.ose_otlp_condattr_columns(h)
+        self.condattr_cols = native.CondAttrColumns.from_buffer_copy(p.contents) if p else None
+
+    def condattr_download(self) -> dict:
+        """Host copies (numpy, uint8) of the columns of condattr_cols and the arena."""
+        c = self.condattr_cols
+        if c is None:
+            raise native.OseError(native.OSE_EINVAL, "the batch has no odigosconditionalattributes columns")
+        K = self.eng.condattr_info().n_keys
+        rows = {"scope": c.n_spans, "scope_resource": c.n_scopes, "scope_name": c.n_scopes, "span_has": K * c.n_spans,
+                "span_val": K * c.n_spans, "span_kv_size": K * c.n_spans, "scope_has": K * c.n_scopes,
+                "scope_val": K * c.n_scopes, "res_has": K * c.n_resources, "res_val": K * c.n_resources,
+                "span_size": c.n_spans}
+        dst = native.CondAttrColumns()
+        dst.n_spans, dst.n_resources, dst.n_scopes, dst.arena_bytes = c.n_spans, c.n_resources, c.n_scopes, c.arena_bytes
+        out = {"arena": np.zeros(c.arena_bytes + 16, dtype=np.uint8)}
+        for name, cnt in rows.items():
+            out[name] = np.zeros(max(1, cnt * CONDATTR_COLUMNS[name]) + 16, dtype=np.uint8)
+        for name, a in out.items():
+            setattr(dst, name, a.ctypes.data)
+        native.check(self.L.ose_otlp_condattr_download(self.h, C.byref(dst)))
+        return out
 
     def attrset(self, k: int) -> dict:
         import json
@@ -683,6 +728,7 @@ class ReleasedOtlpBatch(OtlpBatch):
         self.h = h
         self.cols = native.Columns.from_buffer_copy(self.L.ose_otlp_columns(h).contents)
         self.outs, self.o = device_outputs(self.cols, tmpl_cap=tmpl_cap)
+        self.condattr_cols = None   # (ose_otlp_condattr_columns is NULL for a store's batch)
 
     def close(self):
         self.h = None

@@ -233,6 +233,20 @@ void columnize_span(const ColumnizeCtx& c, const Span& sp, const std::vector<uin
 // processSpan's reads (odigosconditionalattributes/processor.go:43-126) as
 // columns: per key, Map.Get on the span, scope and resource maps (:68, :80-84)
 // and AsString of what it finds (:69, :90), plus the scope names (:36).
+void condattr_lookup(const std::vector<std::string>& keys, const AttrMap& m, size_t row, size_t rows, std::string& arena,
+                     size_t arena_base, const ProtoSizer& sizer, uint8_t* has, ose_strref* val, uint32_t* kv_size) {
+  for (size_t k = 0; k < keys.size(); k++) {
+    const Value* v = m.Get(keys[k]);
+    if (!v) continue;
+    const size_t at = arena.size();
+    if (v->type == Value::TStr) arena += v->s;
+    else arena += v->AsString();
+    has[k * rows + row] = 1;
+    val[k * rows + row] = ose_strref{(uint32_t)(arena_base + at), (uint32_t)(arena.size() - at)};
+    if (kv_size) kv_size[k * rows + row] = (uint32_t)field_len(sizer.key_value(keys[k], *v));
+  }
+}
+
 void columnize_condattr(const std::vector<std::string>& keys, size_t n_targets, const Traces& t, const ProtoSizer& sizer,
                         CondAttrHostCols& o) {
   const size_t K = keys.size(), R = t.resource_spans.size();
@@ -242,13 +256,6 @@ void columnize_condattr(const std::vector<std::string>& keys, size_t n_targets, 
     for (auto& ss : rs.scope_spans) N += ss.spans.size();
   }
   std::string arena;
-  auto add = [&](const Value& v) {
-    ose_strref r{(uint32_t)arena.size(), 0};
-    if (v.type == Value::TStr) arena += v.s;
-    else arena += v.AsString();
-    r.len = (uint32_t)(arena.size() - r.off);
-    return r;
-  };
   auto pad = [](size_t x) { return std::max<size_t>(x, 1); };   // data() never NULL
   o.scope.assign(pad(N), 0);
   o.scope_resource.assign(pad(S), 0);
@@ -263,28 +270,15 @@ void columnize_condattr(const std::vector<std::string>& keys, size_t n_targets, 
   size_t i = 0, si = 0;
   for (size_t ri = 0; ri < R; ri++) {
     const ResourceSpans& rs = t.resource_spans[ri];
-    for (size_t k = 0; k < K; k++)
-      if (const Value* v = rs.resource_attrs.Get(keys[k])) {
-        o.res_has[k * R + ri] = 1;
-        o.res_val[k * R + ri] = add(*v);
-      }
+    condattr_lookup(keys, rs.resource_attrs, ri, R, arena, 0, sizer, o.res_has.data(), o.res_val.data(), nullptr);
     for (auto& ss : rs.scope_spans) {
       o.scope_resource[si] = (uint32_t)ri;
       o.scope_name[si] = ose_strref{(uint32_t)arena.size(), (uint32_t)ss.scope_name.size()};
       arena += ss.scope_name;
-      for (size_t k = 0; k < K; k++)
-        if (const Value* v = ss.scope_attrs.Get(keys[k])) {
-          o.scope_has[k * S + si] = 1;
-          o.scope_val[k * S + si] = add(*v);
-        }
+      condattr_lookup(keys, ss.scope_attrs, si, S, arena, 0, sizer, o.scope_has.data(), o.scope_val.data(), nullptr);
       for (auto& sp : ss.spans) {
         o.scope[i] = (uint32_t)si;
-        for (size_t k = 0; k < K; k++)
-          if (const Value* v = sp.attrs.Get(keys[k])) {
-            o.span_has[k * N + i] = 1;
-            o.span_val[k * N + i] = add(*v);
-            o.span_kv_size[k * N + i] = (uint32_t)field_len(sizer.key_value(keys[k], *v));
-          }
+        condattr_lookup(keys, sp.attrs, i, N, arena, 0, sizer, o.span_has.data(), o.span_val.data(), o.span_kv_size.data());
         i++;
       }
       si++;

@@ -92,5 +92,12 @@ struct CondAttrHostCols {
 };
 void columnize_condattr(const std::vector<std::string>& keys, size_t n_targets, const Traces& t, const ProtoSizer& sizer,
                         CondAttrHostCols& out);
+// Map.Get(key) of every key on one attribute map, as entry [k * rows + row]
+// of key-major columns: has, val = the value's AsString appended to `arena`
+// (a ref from arena_base on) and, when kv_size is not NULL, the KeyValue's
+// framed size in a span (field 9).  The one lookup of columnize_condattr and
+// of the OTLP decoder's host-made columns (otlp_host.cpp).
+void condattr_lookup(const std::vector<std::string>& keys, const AttrMap& m, size_t row, size_t rows, std::string& arena,
+                     size_t arena_base, const ProtoSizer& sizer, uint8_t* has, ose_strref* val, uint32_t* kv_size);
 
 }  // namespace ose

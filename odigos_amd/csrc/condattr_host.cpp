@@ -165,8 +165,42 @@ void release_condattr(Engine* e) {
   if (e->condattr_blob_dev) (void)hipFree(e->condattr_blob_dev);
   if (e->condattr_pin) (void)hipHostFree(e->condattr_pin);
   if (e->condattr_stage) (void)hipFree(e->condattr_stage);
+  if (e->condattr_slots_dev) (void)hipFree(e->condattr_slots_dev);
+  e->condattr_slots_dev = nullptr;
   e->condattr_blob_dev = nullptr;
   e->condattr_pin = e->condattr_stage = nullptr;
+}
+
+// The table otlp_condattr_kernel finds a span's attribute keys in: open
+// addressing on the key bytes' FNV-1a (the hash of condattr_device.hpp), load
+// <= 1/2 so that a probe run ends at an empty slot, and the set of key lengths.
+int build_condattr_keytab(Engine* e) {
+  std::lock_guard<std::mutex> g(e->condattr_mu);
+  if (e->condattr_slots_dev) return 0;
+  if (const int brc = bind_device(e)) return brc;
+  const std::vector<std::string>& keys = e->condattr_tab.keys;
+  uint32_t cap = 2;
+  while ((uint64_t)cap < 2 * (uint64_t)keys.size()) cap <<= 1;
+  std::vector<OtlpCaSlot> slots(cap, OtlpCaSlot{0, condattr::kNone});
+  uint64_t lens = 0;
+  for (size_t k = 0; k < keys.size(); k++) {
+    const uint32_t h = condattr::hash_bytes_host(reinterpret_cast<const uint8_t*>(keys[k].data()), (uint32_t)keys[k].size());
+    uint32_t p = h & (cap - 1);
+    while (slots[p].key != condattr::kNone) p = (p + 1) & (cap - 1);
+    slots[p] = OtlpCaSlot{h, (uint32_t)k};
+    lens |= 1ull << std::min<size_t>(keys[k].size(), 63);
+  }
+  void* d = nullptr;
+  HIP_TRY(hipMalloc(&d, slots.size() * sizeof(OtlpCaSlot)));
+  const hipError_t he = hipMemcpy(d, slots.data(), slots.size() * sizeof(OtlpCaSlot), hipMemcpyHostToDevice);
+  if (he != hipSuccess) {
+    (void)hipFree(d);
+    return fail(OSE_EDEVICE, std::string("engine option otlp_condattr: ") + hipGetErrorString(he));
+  }
+  e->condattr_slot_mask = cap - 1;
+  e->condattr_key_lens = lens;
+  e->condattr_slots_dev = d;
+  return 0;
 }
 
 namespace {

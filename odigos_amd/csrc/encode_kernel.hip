@@ -22,6 +22,7 @@
 // host encoder re-marshals — sets a flag and the host encoder runs instead.
 #include <hip/hip_runtime.h>
 
+#include "condattr_device.hpp"
 #include "device_common.hpp"
 #include "kernels.hpp"
 #include "pb_device.hpp"
@@ -224,6 +225,119 @@ __device__ __forceinline__ void enc_span_body(const EncArgs& a) {
 }
 __global__ __launch_bounds__(kERec) void enc_span_kernel(EncArgs a) { enc_span_body<false>(a); }
 __global__ __launch_bounds__(kERec) void enc_span_sql_kernel(EncArgs a) { enc_span_body<true>(a); }
+
+// ---- sizing: spans with odigosconditionalattributes' puts ----------------------
+// ose_otlp_encode_condattr (Enc::rewrite_ca / plan_ca in otlp_encode.cpp):
+// kernels of their own beside the plain and the SQL instances, with an
+// argument block of their own (EncCaArgs), so a call without the stage runs the
+// code and passes the arguments it did before.  A span's puts are a mask of
+// target numbers (at most kEncCaTargets of them: the per-span state is that
+// mask and a length, in registers), each put's name in the compiled config's
+// blob and its value behind src / val.
+namespace {
+// bit u: span i has a put for target u
+__device__ __forceinline__ uint32_t ca_put_mask(const EncCaArgs& a, uint64_t i) {
+  uint32_t m = 0;
+  for (uint32_t u = 0; u < a.ca_targets; u++) m |= (a.ca_src[u * a.n_spans + i] != OSE_CA_KEEP ? 1u : 0u) << u;
+  return m;
+}
+// Of the targets in `open`, the one whose name is the key of the KeyValue
+// [po, po + pl) (32: none of them); *bad on a malformed KeyValue.
+__device__ uint32_t ca_match(const condattr::View& v, const uint8_t* pb, uint32_t po, uint32_t pl, uint32_t open, bool* bad) {
+  Rd kv(pb, po, po + pl);
+  uint32_t ko = 0, kl = 0;
+  while (kv.more()) {
+    uint32_t kf, kwt;
+    if (!kv.tag(kf, kwt)) break;
+    if (kwt == 2 && kf == 1) {
+      uint32_t o, l;
+      if (!kv.len(o, l)) break;
+      ko = o, kl = l;
+    } else {
+      kv.skip(kwt);
+    }
+  }
+  if (kv.bad) { *bad = true; return 32; }
+  while (open) {
+    const uint32_t u = (uint32_t)__builtin_ctz(open);
+    open &= open - 1;
+    const condattr::Key key = v.keys[v.targets[u].key];
+    if (key.len != kl) continue;
+    const uint8_t* s = v.strings + key.off;
+    uint32_t q = 0;
+    while (q < kl && kv.br.at(ko + q) == s[q]) q++;
+    if (q == kl) return u;
+  }
+  return 32;
+}
+}  // namespace
+
+__global__ __launch_bounds__(kERec) void enc_span_ca_kernel(EncCaArgs a) {
+  const condattr::View v = condattr::view(a.ca_blob);
+  const uint64_t stride = (uint64_t)gridDim.x * kERec, n = a.n_spans;
+  uint32_t fb = 0;
+  for (uint64_t i = (uint64_t)blockIdx.x * kERec + threadIdx.x; i < n; i += stride) {
+    const uint64_t ref = a.span_ref[i];
+    const uint32_t off = (uint32_t)ref, L = (uint32_t)(ref >> 32);
+    a.span_out[i] = (uint32_t)field_len(L);
+    // the puts: their mask, what they add, and what the host reports (a src
+    // beyond OSE_CA_CONFIG, a ref beyond its buffer: nothing is read there)
+    uint32_t open = 0;
+    uint64_t out = L;
+    bool refuse = false;
+    for (uint32_t u = 0; u < a.ca_targets; u++) {
+      const uint32_t s = a.ca_src[u * n + i];
+      if (s == OSE_CA_KEEP) continue;
+      const ose_strref val = a.ca_val[u * n + i];
+      if (s > OSE_CA_CONFIG || (uint64_t)val.off + val.len > (s == OSE_CA_ARENA ? a.ca_arena_bytes : a.ca_string_bytes)) {
+        refuse = true;
+        break;
+      }
+      open |= 1u << u;
+      out += condattr::kv_framed(v.targets[u].name_len, val.len);
+    }
+    if (refuse) {
+      fb |= kEncFbCa;
+      continue;
+    }
+    if (a.span_size[i] != L) {   // Enc::rewrite_ca re-marshals it (with or without a put, as Enc::rewritten)
+      fb |= kEncFbSpan;
+      continue;
+    }
+    if (!open) continue;   // verbatim
+    // plan_ca: fields ascend; the first KeyValue of a put target is replaced
+    uint32_t prev_f = 0;
+    bool ok = true;
+    Rd r(a.pb, off, off + L);
+    while (r.more()) {
+      const uint32_t a0 = r.i;
+      uint32_t f, wt, po = 0, pl = 0;
+      if (!r.tag(f, wt)) break;
+      if (f < prev_f) { ok = false; break; }   // out of order: re-marshaled by the host
+      prev_f = f;
+      if (wt == 2) {
+        if (!r.len(po, pl)) break;
+      } else if (!r.skip(wt)) {
+        break;
+      }
+      if (f != 9 || wt != 2 || !open) continue;
+      bool bad = false;
+      const uint32_t u = ca_match(v, a.pb, po, pl, open, &bad);
+      if (bad) { ok = false; break; }
+      if (u < 32) {
+        open &= ~(1u << u);
+        out -= r.i - a0;
+      }
+    }
+    if (!ok || r.bad || r.i != off + L) {   // re-marshaled, or malformed (the host reports it)
+      fb |= kEncFbSpan;
+      continue;
+    }
+    a.ca_len[i] = (uint32_t)out;
+    a.span_out[i] = (uint32_t)field_len(out);
+  }
+  if (fb) flag(a, fb);
+}
 
 // ---- sizing: scopes ------------------------------------------------------------
 // Enc::size_chunk's scope loop: header (pdata always writes the
@@ -585,9 +699,70 @@ __device__ void write_edit(const EncArgs& a, WaveOut& w, const uint8_t* sp, uint
   w.copy(sp + b2, L - b2);
 }
 
+// PutStr(target u, value) of span i as a Span.attributes field: the key omitted
+// when "", the value framed and its string oneof written even when empty
+__device__ void write_put(const EncCaArgs& a, const condattr::View& v, WaveOut& w, uint32_t u, uint64_t i) {
+  const condattr::Key key = v.keys[v.targets[u].key];
+  const uint32_t s = a.ca_src[u * a.n_spans + i];
+  const ose_strref val = a.ca_val[u * a.n_spans + i];
+  const uint8_t* vb = (s == OSE_CA_CONFIG ? v.strings : a.pb) + val.off;   // (the arena starts with the message)
+  w.hdr(0x4A, str_field(key.len) + field_len(field_len(val.len)));
+  if (key.len) {
+    w.hdr(0x0A, key.len);
+    w.copy(v.strings + key.off, key.len);
+  }
+  w.hdr(0x12, field_len(val.len));
+  w.hdr(0x0A, val.len);
+  w.copy(vb, val.len);
+}
+
+// Enc::plan_ca's writing: the span [off, off + L) of index i with the puts of
+// `open` (every lane walks the same bytes: the walk is wave-uniform)
+__device__ void write_ca(const EncCaArgs& a, WaveOut& w, uint32_t off, uint32_t L, uint32_t open, uint64_t i) {
+  const condattr::View v = condattr::view(a.ca_blob);
+  const uint8_t* sp = a.pb + off;
+  uint32_t copied = 0;
+  Rd r(a.pb, off, off + L);
+  while (r.more() && open) {
+    const uint32_t a0 = r.i - off;
+    uint32_t f, wt, po = 0, pl = 0;
+    if (!r.tag(f, wt)) break;
+    if (f > 9) {   // after the last attribute: the targets still unplaced, in target order
+      w.copy(sp + copied, a0 - copied);
+      copied = a0;
+      while (open) {
+        write_put(a, v, w, (uint32_t)__builtin_ctz(open), i);
+        open &= open - 1;
+      }
+      break;
+    }
+    if (wt == 2) {
+      if (!r.len(po, pl)) break;
+    } else if (!r.skip(wt)) {
+      break;
+    }
+    if (f != 9 || wt != 2) continue;
+    bool bad = false;
+    const uint32_t u = ca_match(v, a.pb, po, pl, open, &bad);
+    if (u < 32) {
+      w.copy(sp + copied, a0 - copied);
+      write_put(a, v, w, u, i);
+      copied = r.i - off;
+      open &= ~(1u << u);
+    }
+  }
+  w.copy(sp + copied, L - copied);
+  while (open) {   // no field after the attributes
+    write_put(a, v, w, (uint32_t)__builtin_ctz(open), i);
+    open &= open - 1;
+  }
+}
+
 // the record of resource r at dst (Enc::write_chunk)
-template <bool kSql>
-__device__ void write_record(const EncArgs& a, uint64_t r, uint8_t* dst, uint64_t rec) {
+// kCa (A = EncCaArgs): the spans with odigosconditionalattributes' puts are
+// written by write_ca; without, the code is what it was before
+template <bool kSql, bool kCa = false, class A = EncArgs>
+__device__ void write_record(const A& a, uint64_t r, uint8_t* dst, uint64_t rec) {
   WaveOut w{dst, 0, rec, (int)(threadIdx.x & 63)};
   w.hdr(0x0A, uni64(a.res_body[r]));
   const uint64_t h = uni64(a.res_hdr[r]);
@@ -614,7 +789,8 @@ __device__ void write_record(const EncArgs& a, uint64_t r, uint8_t* dst, uint64_
         const uint64_t ref = a.span_ref[j];
         roff = (uint32_t)ref;
         rlen = (uint32_t)(ref >> 32);
-        u = (a.url_out ? a.url_out[j] : 0u) | (kSql ? (uint32_t)a.sql_op[j] << 8 : 0u);   // 0: verbatim
+        if constexpr (kCa) u = ca_put_mask(a, j);
+        else u = (a.url_out ? a.url_out[j] : 0u) | (kSql ? (uint32_t)a.sql_op[j] << 8 : 0u);   // 0: verbatim
       }
       uint64_t kept = __ballot(so != 0);
       while (kept) {
@@ -624,6 +800,9 @@ __device__ void write_record(const EncArgs& a, uint64_t r, uint8_t* dst, uint64_
         if (lane32(u, b) == 0) {
           w.hdr(0x12, L);
           w.copy(a.pb + off, L);
+        } else if constexpr (kCa) {
+          w.hdr(0x12, uni32(a.ca_len[c + (uint64_t)b]));
+          write_ca(a, w, off, L, lane32(u, b), c + (uint64_t)b);
         } else {
           const EncEdit* ep = a.edit + c + (uint64_t)b;
           EncEdit e;
@@ -666,8 +845,8 @@ __device__ void write_record(const EncArgs& a, uint64_t r, uint8_t* dst, uint64_
 }  // namespace
 
 // a wave per resource (grid-stride), its record to every output it routes to
-template <bool kSql>
-__device__ __forceinline__ void enc_write_body(const EncArgs& a) {
+template <bool kSql, bool kCa = false, class A = EncArgs>
+__device__ __forceinline__ void enc_write_body(const A& a) {
   const uint64_t waves = (uint64_t)gridDim.x * (kERec / kWave);
   for (uint64_t r = uni64((uint64_t)blockIdx.x * (kERec / kWave) + (threadIdx.x >> 6)); r < a.n_res; r += waves) {
     const uint64_t rec = uni64(a.res_rec[r]);
@@ -676,12 +855,13 @@ __device__ __forceinline__ void enc_write_body(const EncArgs& a) {
     while (mask) {
       const uint32_t k = (uint32_t)__builtin_ctzll(mask);
       mask &= mask - 1;
-      write_record<kSql>(a, r, a.out + a.out_base[k] + uni64(a.off[(uint64_t)k * a.n_res + r]), rec);
+      write_record<kSql, kCa, A>(a, r, a.out + a.out_base[k] + uni64(a.off[(uint64_t)k * a.n_res + r]), rec);
     }
   }
 }
 __global__ __launch_bounds__(kERec) void enc_write_kernel(EncArgs a) { enc_write_body<false>(a); }
 __global__ __launch_bounds__(kERec) void enc_write_sql_kernel(EncArgs a) { enc_write_body<true>(a); }
+__global__ __launch_bounds__(kERec) void enc_write_ca_kernel(EncCaArgs a) { enc_write_body<false, true, EncCaArgs>(a); }
 
 // ---- launchers ---------------------------------------------------------------------
 namespace {
@@ -713,6 +893,12 @@ void launch_enc_write(const EncArgs& a, hipStream_t st) {
   if (!a.n_res) return;
   if (a.sql_op) hipLaunchKernelGGL(enc_write_sql_kernel, dim3(grid_of(a.n_res * kWave, 16384)), dim3(kERec), 0, st, a);
   else hipLaunchKernelGGL(enc_write_kernel, dim3(grid_of(a.n_res * kWave, 16384)), dim3(kERec), 0, st, a);
+}
+void launch_enc_spans_ca(const EncCaArgs& a, hipStream_t st) {
+  if (a.n_spans) hipLaunchKernelGGL(enc_span_ca_kernel, dim3(grid_of(a.n_spans, 8192)), dim3(kERec), 0, st, a);
+}
+void launch_enc_write_ca(const EncCaArgs& a, hipStream_t st) {
+  if (a.n_res) hipLaunchKernelGGL(enc_write_ca_kernel, dim3(grid_of(a.n_res * kWave, 16384)), dim3(kERec), 0, st, a);
 }
 
 }  // namespace ose

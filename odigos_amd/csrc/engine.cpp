@@ -973,11 +973,18 @@ int ose_engine_set_option(ose_engine* eng, const char* name, int64_t value) {
       {"encode_host", Engine::kOptEncodeHost},
       {"otlp_sqlop", Engine::kOptOtlpSqlop},
       {"url_path_counts", Engine::kOptUrlPathCounts},
+      {"otlp_condattr", Engine::kOptOtlpCondattr},
   };
   for (const auto& o : kOpts) {
     if (strcmp(name, o.name) != 0) continue;
     if (o.bit == Engine::kOptOtlpSqlop && !e->has_sqlop)
       return fail(OSE_EINVAL, "engine option otlp_sqlop: odigossqldboperationprocessor is not configured");
+    if (o.bit == Engine::kOptOtlpCondattr) {
+      if (!e->has_condattr)
+        return fail(OSE_EINVAL, "engine option otlp_condattr: odigosconditionalattributes is not configured");
+      if (value)
+        if (const int rc = build_condattr_keytab(e)) return rc;
+    }
     if (value) e->options.fetch_or(o.bit);
     else e->options.fetch_and(~o.bit);
     return 0;

@@ -50,6 +50,7 @@ struct OtlpEngine;
 void release_otlp(Engine* e);                      // otlp_host.cpp
 void release_encode(Engine* e);                    // otlp_encode.cpp
 void release_condattr(Engine* e);                  // condattr_host.cpp
+int build_condattr_keytab(Engine* e);              // condattr_host.cpp (engine option otlp_condattr)
 
 // What the groupbytrace store (gbt_host.cpp) reads of a decoded ose_otlp_batch
 // and writes into the one it releases (otlp_host.cpp owns the type).
@@ -159,6 +160,12 @@ struct Engine {
   void* condattr_pin = nullptr;
   void* condattr_stage = nullptr;
   size_t condattr_pin_cap = 0, condattr_stage_cap = 0;
+  // engine option otlp_condattr: the key table otlp_condattr_kernel looks the
+  // span's attribute keys up in (OtlpCaSlot[condattr_slot_mask + 1] on the
+  // device), built when the option is first set
+  void* condattr_slots_dev = nullptr;
+  uint32_t condattr_slot_mask = 0;
+  uint64_t condattr_key_lens = 0;
   // ose_engine_set_option: alternative implementations of the OTLP legs
   // (the default path is the fast one; these select the others, for tests
   // that compare the two)
@@ -166,7 +173,10 @@ struct Engine {
   // path carries odigossqldboperationprocessor (off until the next ABI version)
   enum : uint32_t {
     kOptOtlpGpuChain = 1, kOptOtlpHostResources = 2, kOptOtlpHostScopes = 4, kOptEncodeHost = 8, kOptOtlpSqlop = 16,
-    kOptUrlPathCounts = 32   // run_url keeps the call's unplanned / slow list lengths (ose_engine_path_counts)
+    kOptUrlPathCounts = 32,  // run_url keeps the call's unplanned / slow list lengths (ose_engine_path_counts)
+    // a feature switch like kOptOtlpSqlop: the OTLP path carries odigosconditionalattributes
+    // (ose_otlp_condattr_columns, ose_otlp_encode_condattr)
+    kOptOtlpCondattr = 64
   };
   std::atomic<uint32_t> options{0};
   bool option(uint32_t o) const { return (options.load(std::memory_order_relaxed) & o) != 0; }

@@ -74,10 +74,17 @@ const char* kQuery[] = {
 };
 
 struct Res { uint64_t first, count; };
+// the InstrumentationScope names to draw from (osegen_otlp_scoped): resource r's
+// scope takes names[mix(r) % n]; none: the net/http instrumentation's name
+struct ScopeNames {
+  const char* bytes = nullptr;
+  const uint32_t* lens = nullptr;
+  std::vector<uint64_t> offs;
+};
 
 // sql_every != 0: one span in sql_every also carries a db.query.text (its last attribute)
 void encode_resources(const ose_columns* c, const std::vector<Res>& res, size_t r0, size_t r1, std::string& out,
-                      uint32_t sql_every) {
+                      uint32_t sql_every, const ScopeNames& names) {
   std::string rs, sc, sp, tmp;
   for (size_t r = r0; r < r1; r++) {
     rs.clear();
@@ -98,7 +105,12 @@ void encode_resources(const ose_columns* c, const std::vector<Res>& res, size_t 
     sc.clear();
     {   // InstrumentationScope
       std::string scm;
-      put_str(scm, 1, "go.opentelemetry.io/contrib/instrumentation/net/http");
+      if (names.offs.empty()) {
+        put_str(scm, 1, "go.opentelemetry.io/contrib/instrumentation/net/http");
+      } else {
+        const size_t k = (size_t)(mix(r ^ 0x5C09E) % names.offs.size());
+        put_str(scm, 1, std::string(names.bytes + names.offs[k], names.lens[k]));
+      }
       put_str(scm, 2, "0.53.0");
       put_msg(sc, 1, scm);
     }
@@ -174,7 +186,10 @@ extern "C" {
 // in resource order, one scope per resource).  *len receives the size;
 // free with osegen_otlp_free.  osegen_otlp_sql: the same with a db.query.text
 // on one span in sql_every (0: none), for the odigossqldboperationprocessor legs.
-char* osegen_otlp_sql(const ose_columns* c, int threads, uint64_t* len, uint32_t sql_every) {
+// osegen_otlp_scoped: the same with every resource's scope name drawn from
+// n_names names (their bytes back to back in `names`, lengths in name_lens),
+// for the odigosconditionalattributes legs.
+static char* otlp_bytes(const ose_columns* c, int threads, uint64_t* len, uint32_t sql_every, const ScopeNames& names) {
   std::vector<Res> res(c->n_resources, Res{0, 0});
   for (uint64_t i = 0; i < c->n_spans; i++) {
     const uint32_t r = c->resource[i];
@@ -186,7 +201,7 @@ char* osegen_otlp_sql(const ose_columns* c, int threads, uint64_t* len, uint32_t
   std::vector<std::string> parts((size_t)threads);
   std::vector<std::thread> th;
   for (int t = 0; t < threads; t++)
-    th.emplace_back([&, t]() { encode_resources(c, res, R * t / threads, R * (t + 1) / threads, parts[t], sql_every); });
+    th.emplace_back([&, t]() { encode_resources(c, res, R * t / threads, R * (t + 1) / threads, parts[t], sql_every, names); });
   for (auto& x : th) x.join();
   uint64_t total = 0;
   for (auto& p : parts) total += p.size();
@@ -198,6 +213,23 @@ char* osegen_otlp_sql(const ose_columns* c, int threads, uint64_t* len, uint32_t
   }
   *len = total;
   return out;
+}
+
+char* osegen_otlp_sql(const ose_columns* c, int threads, uint64_t* len, uint32_t sql_every) {
+  return otlp_bytes(c, threads, len, sql_every, ScopeNames{});
+}
+
+char* osegen_otlp_scoped(const ose_columns* c, int threads, uint64_t* len, uint32_t sql_every, const char* names,
+                         const uint32_t* name_lens, uint32_t n_names) {
+  ScopeNames sn;
+  sn.bytes = names;
+  sn.lens = name_lens;
+  uint64_t off = 0;
+  for (uint32_t k = 0; k < n_names; k++) {
+    sn.offs.push_back(off);
+    off += name_lens[k];
+  }
+  return otlp_bytes(c, threads, len, sql_every, sn);
 }
 
 char* osegen_otlp(const ose_columns* c, int threads, uint64_t* len) { return osegen_otlp_sql(c, threads, len, 0); }

@@ -703,6 +703,8 @@ enum : uint32_t {
   kEncFbTmpl = 8,       // a template reference beyond the arena (the host reports it)
   kEncFbRoute = 16,     // a routing attribute the device does not read exactly
   kEncFbWrite = 32,     // the writing pass disagreed with the sizing pass (a bug: the call fails)
+  kEncFbCa = 64,        // odigosconditionalattributes: more targets than kEncCaTargets, or a put the host
+                        // reports (a src beyond OSE_CA_CONFIG, a ref beyond its buffer)
 };
 struct EncEdit {        // one rewritten span (otlp_encode.cpp Edit)
   uint32_t name_a, name_b, attr_a, attr_b;
@@ -771,6 +773,26 @@ void launch_enc_scopes(const EncArgs& a, hipStream_t st);
 void launch_enc_resources(const EncArgs& a, hipStream_t st);
 void launch_enc_scan(const EncArgs& a, hipStream_t st);
 void launch_enc_write(const EncArgs& a, hipStream_t st);
+// ... and the instances of ose_otlp_encode_condattr (enc_span_ca_kernel /
+// enc_write_ca_kernel): odigosconditionalattributes' puts, src / val as
+// ose_condattr_outputs (device), the names in the engine's compiled config.
+// The GPU path takes configs of up to kEncCaTargets targets: a span's puts
+// are a bit mask held in a register through the sizing and the writing walk
+// (below 32: ca_match answers 32 for "none"; the shipped category-attributes
+// profile has 3 targets, the tests' adversarial config 17); a config with more
+// goes to the host encoder (kEncFbCa), which has no such bound.
+constexpr uint32_t kEncCaTargets = 24;
+struct EncCaArgs : EncArgs {
+  const uint8_t* ca_blob;        // condattr_device.hpp's blob
+  const uint8_t* ca_src;         // [ca_targets * n_spans]
+  const ose_strref* ca_val;
+  uint32_t ca_targets;
+  uint32_t ca_string_bytes;      // the blob's string table
+  uint64_t ca_arena_bytes;       // the batch arena (pb is its base)
+  uint32_t* ca_len;              // [n_spans] the new length of a span with puts
+};
+void launch_enc_spans_ca(const EncCaArgs& a, hipStream_t st);
+void launch_enc_write_ca(const EncCaArgs& a, hipStream_t st);
 
 struct OtlpFix {
   uint64_t idx;
@@ -829,6 +851,51 @@ struct OtlpSqlFix {
   ose_strref query;
 };
 void launch_otlp_sqlop_fix(const OtlpSqlFix* fix, uint32_t n, uint8_t* db_flags, ose_strref* db_query, hipStream_t st);
+
+// odigosconditionalattributes' span columns from the message
+// (otlp_condattr_kernel.hip; engine option otlp_condattr).  A pass of its own
+// after the span kernel (and otlp_sqlop_kernel), one lane per span: for the
+// first attributes KeyValue of each of the engine's condattr keys span_has = 1,
+// span_val a ref into the message bytes and, for target keys, span_kv_size.
+// span_has is zeroed before the launch; only hits are stored.  The keys are
+// found through a table built when the option is set (OtlpCaSlot[mask + 1],
+// open addressing on the key bytes' FNV-1a, load <= 1/2; key_lens: bit
+// min(len, 63) per key length) over the Key[] and strings of the compiled
+// config's blob (condattr_device.hpp).  A matched key whose value is not a
+// string_value needs AsString: the span joins the host pass's list (unless
+// listed already), and the host pass writes all K entries of every listed span
+// (otlp_condattr_fix_kernel).
+struct OtlpCaSlot { uint32_t hash, key; };   // key == 0xFFFFFFFF: empty
+struct OtlpCondAttrArgs {
+  const uint8_t* pb;            // as OtlpArgs::pb
+  uint64_t n_spans;
+  const uint64_t* span_ref;
+  const uint8_t* blob;          // the engine's compiled config on the device
+  const OtlpCaSlot* slots;
+  uint32_t slot_mask;
+  uint64_t key_lens;
+  uint8_t* span_has;            // [K * n_spans], key-major
+  ose_strref* span_val;
+  uint32_t* span_kv_size;
+  uint8_t* host_flag;           // the span kernel's; 1: skipped here
+  uint32_t* host_count;
+  uint32_t* host_list;
+  uint32_t host_cap;
+};
+void launch_otlp_condattr(const OtlpCondAttrArgs& a, hipStream_t st);
+// the host pass's entries, [k * cnt + q] for key k of listed span list[q]
+struct OtlpCondAttrFixArgs {
+  uint32_t cnt, n_keys;
+  uint64_t n_spans;
+  const uint32_t* list;         // the host list (device)
+  const uint8_t* fix_has;
+  const ose_strref* fix_val;
+  const uint32_t* fix_kv;
+  uint8_t* span_has;
+  ose_strref* span_val;
+  uint32_t* span_kv_size;
+};
+void launch_otlp_condattr_fix(const OtlpCondAttrFixArgs& a, hipStream_t st);
 
 // ---- groupbytrace store (gbt_kernel.hip) --------------------------------------
 struct GbtSlot {              // trace id -> creation number (32 B, generation-tagged)

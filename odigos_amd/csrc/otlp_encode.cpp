@@ -13,6 +13,10 @@
 //     (Map.PutStr on an existing key) or appended after the last attribute;
 //     odigossqldboperationprocessor's db.operation.name is put the same way
 //     after it, and " " + NAME ends the name;
+//   * odigosconditionalattributes' puts (ose_otlp_encode_condattr; a call of
+//     its own, without the URL and SQL decisions) are applied to such a span
+//     on its bytes, in target order: replaced where the key stands, else
+//     after the last attribute;
 //   * any other span (an encoding pdata would not write: unknown fields,
 //     unframed empty ids, non-minimal varints) is decoded and re-marshaled.
 // Resource and scope headers are re-marshaled from their decoded form
@@ -220,7 +224,9 @@ struct Chunk {
   std::deque<ResHdr> rown;          // merged headers (several Resource fields)
   std::deque<std::string> sown;
   std::vector<Edit> edits;          // one per rewritten span, in order
-  std::string mods;                 // re-marshaled spans, AsString methods
+  std::string mods;                 // re-marshaled spans, AsString methods, odigosconditionalattributes' spans
+  std::vector<uint8_t> ca_open;     // plan_ca's per-target state
+  std::string ca_tmp;               // a put value that lies across the arena's two host pieces
   std::vector<uint64_t> out_bytes, out_res, cursor;
   std::string err;
 };
@@ -249,8 +255,24 @@ struct Enc {
   }
   bool kept(uint64_t i) const { return !d.keep || d.keep[i]; }
   bool rewritten(uint64_t i) const {
-    return (d.url_out && d.url_out[i]) || (d.sql_op && d.sql_op[i]) ||
+    return (d.url_out && d.url_out[i]) || (d.sql_op && d.sql_op[i]) || (d.ca_src && ca_puts(i)) ||
            (d.span_size && d.span_size[i] != (uint32_t)(span_ref[i] >> 32));
+  }
+  // odigosconditionalattributes: the span has a put; target u's value
+  bool ca_puts(uint64_t i) const {
+    for (uint32_t u = 0; u < d.ca_targets; u++)
+      if (d.ca_src[u * n + i] != OSE_CA_KEEP) return true;
+    return false;
+  }
+  std::string_view ca_value(Chunk& c, uint32_t u, uint64_t i) const {
+    const ose_strref v = d.ca_val[u * n + i];
+    if (d.ca_src[u * n + i] == OSE_CA_CONFIG) return std::string_view((const char*)d.ca_strings + v.off, v.len);
+    if ((uint64_t)v.off + v.len <= d.ca_tail_base) return std::string_view((const char*)d.ca_arena + v.off, v.len);
+    if (v.off >= d.ca_tail_base) return std::string_view((const char*)d.ca_tail + (v.off - d.ca_tail_base), v.len);
+    const size_t head = (size_t)(d.ca_tail_base - v.off);   // across the two pieces
+    c.ca_tmp.assign((const char*)d.ca_arena + v.off, head);
+    c.ca_tmp.append((const char*)d.ca_tail, v.len - head);
+    return c.ca_tmp;
   }
   void outputs_of(const ResHdr* h, uint32_t* ks, uint32_t& nk) const {
     nk = 0;
@@ -322,6 +344,7 @@ struct Enc {
   bool rewrite(Chunk& c, uint64_t i) {
     const uint8_t* sp = pb + (uint32_t)span_ref[i];
     const size_t L = (size_t)(span_ref[i] >> 32);
+    if (d.ca_src) return rewrite_ca(c, sp, L, i);
     const uint8_t u = d.url_out ? d.url_out[i] : 0;
     std::string_view T;
     if (u) {
@@ -338,6 +361,121 @@ struct Enc {
       if (rc > 0) return true;
     }
     return remarshal(c, sp, L, u, T, op);
+  }
+
+  // odigosconditionalattributes (processor.go:83-98, :113-122, :134): the
+  // span with its puts applied in target order, written to c.mods.  A span in
+  // pdata's encoding is edited on its bytes (plan_ca); any other is decoded,
+  // PutStr'd and re-marshaled, which gives the same bytes.
+  bool rewrite_ca(Chunk& c, const uint8_t* sp, size_t L, uint64_t i) {
+    const size_t start = c.mods.size();
+    const bool canonical = !d.span_size || d.span_size[i] == (uint32_t)L;
+    const int rc = canonical ? plan_ca(c, sp, L, i) : 0;
+    if (rc < 0) return false;
+    if (rc == 0) {
+      c.mods.resize(start);
+      Span s;
+      if (!pb_span(sp, L, s)) { c.err = "OTLP protobuf: malformed Span"; return false; }
+      for (uint32_t u = 0; u < d.ca_targets; u++)
+        if (d.ca_src[u * n + i] != OSE_CA_KEEP) s.attrs.PutStr(d.ca_names[u], ca_value(c, u, i));
+      ProtoWriter(c.mods).span(s);
+    }
+    if (c.mods.size() > 0xFFFFFFFFull) { c.err = "the rewritten spans of one encoder thread pass 4 GiB"; return false; }
+    Edit e{};
+    e.in_mods = 1;
+    e.name_a = (uint32_t)start;
+    e.out_len = (uint32_t)(c.mods.size() - start);
+    c.edits.push_back(e);
+    return true;
+  }
+
+  static void append_varint(std::string& out, uint64_t v) {
+    uint8_t t[10];
+    out.append((const char*)t, (size_t)(put_varint(t, v) - t));
+  }
+  // Span.attributes entry of PutStr(key, v): the key omitted when "", the value
+  // framed and its string oneof written even when empty
+  static void append_put(std::string& out, std::string_view key, std::string_view v) {
+    out.push_back(0x4A);
+    append_varint(out, (key.empty() ? 0 : flen(key.size())) + flen(flen(v.size())));
+    if (!key.empty()) {
+      out.push_back(0x0A);
+      append_varint(out, key.size());
+      out.append(key);
+    }
+    out.push_back(0x12);
+    append_varint(out, flen(v.size()));
+    out.push_back(0x0A);
+    append_varint(out, v.size());
+    out.append(v);
+  }
+
+  // The puts on bytes already in pdata's encoding (fields ascend): the first
+  // KeyValue with a put target's key is replaced where it stands; the targets
+  // still unplaced go after the last attribute, before the first field above
+  // 9, in target order; every other byte is copied.  1 = written to c.mods,
+  // 0 = the fields are out of order (re-marshal), -1 = malformed.
+  int plan_ca(Chunk& c, const uint8_t* sp, size_t L, uint64_t i) {
+    const uint32_t T = d.ca_targets;
+    std::vector<uint8_t>& open = c.ca_open;   // the put targets not yet placed
+    open.assign(T, 0);
+    uint32_t n_open = 0;
+    for (uint32_t u = 0; u < T; u++)
+      if (d.ca_src[u * n + i] != OSE_CA_KEEP) open[u] = 1, n_open++;
+    size_t copied = 0;
+    auto flush = [&](size_t upto) {
+      c.mods.append((const char*)sp + copied, upto - copied);
+      copied = upto;
+    };
+    auto append_open = [&](size_t at) {
+      flush(at);
+      for (uint32_t u = 0; u < T; u++)
+        if (open[u]) append_put(c.mods, d.ca_names[u], ca_value(c, u, i));
+      n_open = 0;
+    };
+    uint32_t prev_f = 0;
+    PbReader r(sp, L);
+    uint32_t f, wt;
+    while (r.more()) {
+      const size_t a = r.i;
+      if (!r.tag(f, wt)) break;
+      if (f < prev_f) return 0;
+      prev_f = f;
+      if (f > 9 && n_open) append_open(a);
+      size_t po = 0, pl = 0;
+      if (wt == 2) {
+        if (!r.bytes(po, pl)) break;
+      } else if (!r.skip(wt, f)) {
+        break;
+      }
+      if (f != 9 || wt != 2 || !n_open) continue;
+      PbReader kv(sp + po, pl);   // KeyValue: the key is field 1
+      uint32_t kf, kwt;
+      size_t ko = 0, kl = 0;
+      while (kv.more() && kv.tag(kf, kwt)) {
+        size_t o, l;
+        if (kwt == 2 && kf == 1) {
+          if (!kv.bytes(o, l)) break;
+          ko = o, kl = l;
+        } else {
+          kv.skip(kwt, kf);
+        }
+      }
+      const std::string_view key((const char*)sp + po + ko, kl);
+      for (uint32_t u = 0; u < T; u++) {
+        if (!open[u] || d.ca_names[u] != key) continue;
+        flush(a);
+        append_put(c.mods, d.ca_names[u], ca_value(c, u, i));
+        copied = r.i;
+        open[u] = 0;
+        n_open--;
+        break;
+      }
+    }
+    if (!r.ok || r.i != L) { c.err = "OTLP protobuf: malformed Span"; return -1; }
+    if (n_open) append_open(L);
+    flush(L);
+    return 1;
   }
 
   // host.cpp Apply (odigosurltemplate processor.go:230-232, 259, then
@@ -869,6 +1007,22 @@ bool encode_traces(const uint8_t* pb, size_t len, const std::vector<uint64_t>& s
   run([&](Chunk& c) { e.write_chunk(c, outs); });
   lap(2);
   return true;
+}
+
+int condattr_check_puts(const uint8_t* src, const ose_strref* val, uint64_t n_spans, uint32_t n_targets,
+                        uint64_t arena_bytes, uint64_t string_bytes, std::string& err) {
+  const uint64_t total = n_spans * n_targets;
+  for (uint64_t q = 0; q < total; q++) {
+    const uint8_t s = src[q];
+    if (s == OSE_CA_KEEP) continue;
+    if (s > OSE_CA_CONFIG) { err = "odigosconditionalattributes: src beyond OSE_CA_CONFIG"; return OSE_EINVAL; }
+    if ((uint64_t)val[q].off + val[q].len > (s == OSE_CA_ARENA ? arena_bytes : string_bytes)) {
+      err = s == OSE_CA_ARENA ? "odigosconditionalattributes: val beyond arena_bytes"
+                              : "odigosconditionalattributes: val beyond the engine's string table";
+      return OSE_ERANGE;
+    }
+  }
+  return 0;
 }
 
 }  // namespace ose

@@ -57,7 +57,28 @@ struct EncodeDecisions {
   uint64_t tmpl_arena_len = 0;
   const uint32_t* span_size = nullptr;  // pdata's size of each span (NULL: trust the input's encoding)
   const uint8_t* sql_op = nullptr;      // OSE_SQLOP_* per span (NULL: no odigossqldboperationprocessor stage)
+  // odigosconditionalattributes (ca_src NULL: no such stage; with it the URL
+  // and SQL decisions are absent).  Per target u and span i, ca_src[u * n + i]
+  // != OSE_CA_KEEP is PutStr(ca_names[u], value), the value's bytes at
+  // ca_val[u * n + i] in ca_arena (OSE_CA_ARENA) or ca_strings (OSE_CA_CONFIG);
+  // the puts of a span apply in target order.  condattr_check_puts has passed.
+  const uint8_t* ca_src = nullptr;
+  const ose_strref* ca_val = nullptr;
+  uint32_t ca_targets = 0;
+  const std::string* ca_names = nullptr;   // [ca_targets]
+  const uint8_t* ca_arena = nullptr;
+  const uint8_t* ca_strings = nullptr;
+  // the arena in two host pieces (ose_otlp_encode_condattr: the caller's
+  // message, and what the decode put behind it): bytes from ca_tail_base on
+  // are at ca_tail
+  uint64_t ca_tail_base = ~0ull;
+  const uint8_t* ca_tail = nullptr;
 };
+
+// 0 when every src is an OSE_CA_* and every put's ref lies inside its buffer;
+// else OSE_EINVAL / OSE_ERANGE and err.
+int condattr_check_puts(const uint8_t* src, const ose_strref* val, uint64_t n_spans, uint32_t n_targets,
+                        uint64_t arena_bytes, uint64_t string_bytes, std::string& err);
 
 struct EncodedOutput {
   std::string name;

@@ -10,9 +10,14 @@
 //   3. otlp_span_kernel decodes every span on the GPU; under the engine option
 //      otlp_sqlop, otlp_sqlop_kernel then reads db.query.text /
 //      db.operation.name (db_flags, db_query) and may add spans to the list;
+//      under otlp_condattr, otlp_condattr_kernel reads the first KeyValue of
+//      each odigosconditionalattributes key (ose_otlp_condattr_columns) and may
+//      add spans too;
 //   4. the spans they list get the host pass: pb_span + columnize_span, their
 //      strings appended after the message bytes, written by otlp_fix_kernel
-//      (and otlp_sqlop_fix_kernel).
+//      (and otlp_sqlop_fix_kernel, otlp_condattr_fix_kernel); under
+//      otlp_condattr the per-scope and per-resource columns of that stage are
+//      then made on the host (condattr_finish).
 #include <algorithm>
 #include <chrono>
 #include <deque>
@@ -227,6 +232,13 @@ struct OtlpBatchImpl {
   // array is the store's; relhost takes the buffer when the host encoder runs
   bool released = false;
   DevBuf relhost;
+  // engine option otlp_condattr (on at the decode: ca_on): the stage's columns
+  // (ose_otlp_condattr_columns) for the engine's ca_keys keys, in a slab of
+  // their own; cafix takes the host pass's entries
+  bool ca_on = false;
+  uint32_t ca_keys = 0;
+  ose_condattr_columns ca{};
+  DevBuf caslab, cafix;
   OtlpBatchImpl() { stage.host = true; emisc.host = true; seth.host = true; relhost.host = true; }
 };
 
@@ -1218,6 +1230,273 @@ int layout_to_host(OtlpBatchImpl* b, hipStream_t st) {
   return 0;
 }
 
+// ---- engine option otlp_condattr: odigosconditionalattributes' columns ----------
+// The span columns on the GPU: the batch's slab of them, span_has zeroed,
+// otlp_condattr_kernel behind the span kernel (before the host-pass count is
+// read back: the kernel may add to the list).
+int condattr_spans(Engine* e, OtlpBatchImpl* b, uint64_t n, const uint64_t* span_ref, uint8_t* host_flag,
+                   uint32_t* host_count, uint32_t* host_list, hipStream_t st) {
+  const size_t K = e->condattr_tab.keys.size();
+  const ose_columns& c = b->cols;
+  const size_t N = std::max<uint64_t>(n, 1), S = std::max<uint32_t>(c.n_scopes, 1), R = std::max<uint32_t>(c.n_resources, 1);
+  ose_condattr_columns& ca = b->ca;
+  ca = ose_condattr_columns{};
+  struct Part { void** dst; size_t bytes; };
+  const Part parts[] = {
+      {(void**)&ca.span_has, K * N}, {(void**)&ca.span_val, 8 * K * N}, {(void**)&ca.span_kv_size, 4 * K * N},
+      {(void**)&ca.scope_name, 8 * S}, {(void**)&ca.scope_has, K * S}, {(void**)&ca.scope_val, 8 * K * S},
+      {(void**)&ca.res_has, K * R}, {(void**)&ca.res_val, 8 * K * R},
+  };
+  size_t total = 0;
+  for (auto& p : parts) total = up(total + p.bytes + 16);
+  int rc;
+  if ((rc = b->caslab.need(total))) return rc;
+  size_t off = 0;
+  for (auto& p : parts) {
+    *p.dst = b->caslab.p + off;
+    off = up(off + p.bytes + 16);
+  }
+  b->ca_keys = (uint32_t)K;
+  if (!n || !K) return 0;
+  HIP_TRY(hipMemsetAsync(const_cast<uint8_t*>(ca.span_has), 0, K * N, st));
+  OtlpCondAttrArgs a{};
+  a.pb = b->arena.p;
+  a.n_spans = n;
+  a.span_ref = span_ref;
+  a.blob = e->condattr_blob_dev;
+  a.slots = static_cast<const OtlpCaSlot*>(e->condattr_slots_dev);
+  a.slot_mask = e->condattr_slot_mask;
+  a.key_lens = e->condattr_key_lens;
+  a.span_has = const_cast<uint8_t*>(ca.span_has);
+  a.span_val = const_cast<ose_strref*>(ca.span_val);
+  a.span_kv_size = const_cast<uint32_t*>(ca.span_kv_size);
+  a.host_flag = host_flag;
+  a.host_count = host_count;
+  a.host_list = host_list;
+  a.host_cap = (uint32_t)N;
+  Engine::Timed tm{};
+  e->prof_begin("otlp_condattr_kernel", st, tm);
+  launch_otlp_condattr(a, st);
+  HIP_TRY(hipGetLastError());
+  e->prof_end(tm, st);
+  return 0;
+}
+
+// The rest, after the host pass: the K entries of every listed span (pb_span
+// and the columniser's lookup, written by otlp_condattr_fix_kernel), and the
+// per-scope and per-resource columns, made on the host from the message bytes
+// at the scopes' InstrumentationScope refs and the resources' Resource fields
+// (S and R are small against N; equal header bytes are looked up once).  The
+// strings go after the arena's bytes (the message, then the host pass's
+// strings); the arena is regrown when they do not fit.
+int condattr_finish(Engine* e, OtlpBatchImpl* b, const uint8_t* pb, const std::vector<uint32_t>& list,
+                    const uint32_t* host_list, hipStream_t st) {
+  const std::vector<std::string>& keys = e->condattr_tab.keys;
+  const size_t K = keys.size();
+  ose_columns& c = b->cols;
+  const uint64_t n = c.n_spans, S = c.n_scopes, R = c.n_resources;
+  const size_t cnt = list.size();
+  // the scopes' and resources' refs: on the host already, or fetched (these
+  // three arrays only: the span refs stay on the device)
+  std::vector<uint64_t> hdr_d, sref_d, rref_d;
+  const uint64_t *hdr = b->lay.scope_hdr.data(), *sref = b->lay.scope_ref.data(), *rref = b->lay.res_ref.data();
+  if (!b->layout_on_host) {
+    hdr_d.resize(S);
+    if (S) HIP_TRY(hipMemcpyAsync(hdr_d.data(), b->d_hdr, 8 * S, hipMemcpyDeviceToHost, st));
+    hdr = hdr_d.data();
+    if (b->res_on_device) {
+      sref_d.resize(S);
+      rref_d.resize(R);
+      if (S) HIP_TRY(hipMemcpyAsync(sref_d.data(), b->d_scope_ref, 8 * S, hipMemcpyDeviceToHost, st));
+      if (R) HIP_TRY(hipMemcpyAsync(rref_d.data(), b->d_res_ref, 8 * R, hipMemcpyDeviceToHost, st));
+      sref = sref_d.data();
+      rref = rref_d.data();
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  // behind the host pass's strings, or, without any, behind the message's 16
+  // zero bytes of slack, where the host pass's would start
+  const size_t base = std::max<size_t>(c.arena_bytes, up(b->pb_len + 16, 16));
+  std::string strs;
+  ProtoSizer sizer;
+  auto pad = [](size_t x) { return std::max<size_t>(x, 1); };
+  std::vector<uint8_t> fix_has(pad(K * cnt), 0), scope_has(pad(K * S), 0), res_has(pad(K * R), 0);
+  std::vector<ose_strref> fix_val(pad(K * cnt), ose_strref{0, 0}), scope_val(pad(K * S), ose_strref{0, 0}),
+      res_val(pad(K * R), ose_strref{0, 0}), scope_name(pad(S), ose_strref{0, 0});
+  std::vector<uint32_t> fix_kv(pad(K * cnt), 0);
+  for (size_t q = 0; q < cnt; q++) {
+    const uint64_t ref = b->span_ref[list[q]];   // (the host pass brought the layout back)
+    Span sp;
+    if (!pb_span(pb + (uint32_t)ref, (size_t)(ref >> 32), sp)) return fail(OSE_EINVAL, "OTLP protobuf: malformed Span");
+    condattr_lookup(keys, sp.attrs, q, cnt, strs, base, sizer, fix_has.data(), fix_val.data(), fix_kv.data());
+  }
+  auto copy_row = [&](std::vector<uint8_t>& has, std::vector<ose_strref>& val, size_t rows, size_t from, size_t to) {
+    for (size_t k = 0; k < K; k++) {
+      has[k * rows + to] = has[k * rows + from];
+      val[k * rows + to] = val[k * rows + from];
+    }
+  };
+  // The scopes and the resources, split over threads (a node's batch may hold
+  // a scope for every few spans): each thread looks equal header bytes up once,
+  // collects its strings with refs relative to them, and the refs are moved to
+  // the strings' final place once every thread's share is known.
+  const int T = (int)std::min<uint64_t>((uint64_t)std::max(1, parallel_width()), std::max<uint64_t>(1, (S + R) / 4096));
+  struct Share { std::string strs, err; };
+  std::vector<Share> share((size_t)T);
+  auto scopes_of = [&](Share& me, size_t s_lo, size_t s_hi) {
+    std::unordered_map<std::string_view, size_t> seen;
+    for (size_t s = s_lo; s < s_hi; s++) {
+      const uint64_t h = hdr[s];
+      ScopeSpans meta;
+      if (h != OtlpLayout::kMulti) {
+        const std::string_view key((const char*)pb + (uint32_t)h, (size_t)(h >> 32));
+        auto it = seen.find(key);
+        if (it != seen.end()) {
+          scope_name[s] = scope_name[it->second];
+          copy_row(scope_has, scope_val, S, it->second, s);
+          continue;
+        }
+        seen.emplace(key, s);
+        if (!pb_scope(pb + (uint32_t)h, (size_t)(h >> 32), meta)) { me.err = "OTLP protobuf: malformed InstrumentationScope"; return; }
+      } else {   // several scope fields: merged, as the encoder's scope_header does
+        const uint64_t sr = sref[s];
+        PbReader r(pb + (uint32_t)sr, (size_t)(sr >> 32));
+        uint32_t f, wt;
+        while (r.more() && r.tag(f, wt)) {
+          size_t o, l;
+          if (f == 1 && wt == 2 && r.bytes(o, l)) {
+            if (!pb_scope(pb + (uint32_t)sr + o, l, meta)) { me.err = "OTLP protobuf: malformed InstrumentationScope"; return; }
+          } else if (f != 1) {
+            r.skip(wt, f);
+          } else {
+            r.fail();
+          }
+        }
+        if (!r.ok) { me.err = "OTLP protobuf: malformed ScopeSpans"; return; }
+      }
+      scope_name[s] = ose_strref{(uint32_t)me.strs.size(), (uint32_t)meta.scope_name.size()};
+      me.strs += meta.scope_name;
+      condattr_lookup(keys, meta.scope_attrs, s, S, me.strs, 0, sizer, scope_has.data(), scope_val.data(), nullptr);
+    }
+  };
+  auto resources_of = [&](Share& me, size_t r_lo, size_t r_hi) {
+    std::unordered_map<std::string_view, size_t> seen;
+    std::vector<std::pair<size_t, size_t>> rf;   // the Resource fields (merged when several)
+    for (size_t ri = r_lo; ri < r_hi; ri++) {
+      const size_t ro = (uint32_t)rref[ri], rl = (size_t)(rref[ri] >> 32);
+      PbReader p(pb + ro, rl);
+      rf.clear();
+      uint32_t f, wt;
+      while (p.more() && p.tag(f, wt)) {
+        size_t o, l;
+        if (wt == 2 && f == 1) {
+          if (!p.bytes(o, l)) break;
+          rf.emplace_back(ro + o, l);
+        } else {
+          p.skip(wt, f);
+        }
+      }
+      if (!p.ok) { me.err = "OTLP protobuf: malformed ResourceSpans"; return; }
+      if (rf.size() == 1) {
+        const std::string_view key((const char*)pb + rf[0].first, rf[0].second);
+        auto it = seen.find(key);
+        if (it != seen.end()) {
+          copy_row(res_has, res_val, R, it->second, ri);
+          continue;
+        }
+        seen.emplace(key, ri);
+      }
+      AttrMap attrs;
+      uint32_t dropped = 0;
+      for (auto& x : rf)
+        if (!pb_resource(pb + x.first, x.second, attrs, dropped)) { me.err = "OTLP protobuf: malformed Resource"; return; }
+      condattr_lookup(keys, attrs, ri, R, me.strs, 0, sizer, res_has.data(), res_val.data(), nullptr);
+    }
+  };
+  parallel_run(T, [&](int t) {
+    scopes_of(share[(size_t)t], S * t / T, S * (t + 1) / T);
+    if (share[(size_t)t].err.empty()) resources_of(share[(size_t)t], R * t / T, R * (t + 1) / T);
+  });
+  for (auto& sh : share)
+    if (!sh.err.empty()) return fail(OSE_EINVAL, sh.err);
+  std::vector<size_t> share_at((size_t)T);
+  {
+    size_t at = base + strs.size();
+    for (int t = 0; t < T; t++) {
+      share_at[(size_t)t] = at;
+      at += share[(size_t)t].strs.size();
+    }
+    if (at > 0xFFFFFFF0ull) return fail(OSE_ERANGE, "OTLP ingest: the arena passes 4 GiB");
+  }
+  parallel_run(T, [&](int t) {
+    const uint32_t add = (uint32_t)share_at[(size_t)t];
+    for (size_t s = S * t / T; s < S * (t + 1) / T; s++) {
+      scope_name[s].off += add;
+      for (size_t k = 0; k < K; k++)
+        if (scope_has[k * S + s]) scope_val[k * S + s].off += add;
+    }
+    for (size_t ri = R * t / T; ri < R * (t + 1) / T; ri++)
+      for (size_t k = 0; k < K; k++)
+        if (res_has[k * R + ri]) res_val[k * R + ri].off += add;
+  });
+  for (auto& sh : share) strs += sh.strs;
+  const size_t end = base + strs.size();
+  if (end > 0xFFFFFFF0ull) return fail(OSE_ERANGE, "OTLP ingest: the arena passes 4 GiB");
+  int rc;
+  if (end + 16 > b->arena.cap) {   // a larger arena: what it holds moves with it
+    DevBuf bigger;
+    if ((rc = bigger.need(end + 16))) return rc;
+    if (base) HIP_TRY(hipMemcpyAsync(bigger.p, b->arena.p, base, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    std::swap(b->arena.p, bigger.p);
+    std::swap(b->arena.cap, bigger.cap);
+    c.arena = b->arena.p;
+    b->walk_info[7] = 1;
+  }
+  ose_condattr_columns& ca = b->ca;
+  auto upl = [&](const void* dst, const void* src, size_t bytes) {
+    return bytes ? hipMemcpyAsync(const_cast<void*>(dst), src, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
+  };
+  HIP_TRY(upl(b->arena.p + base, strs.data(), strs.size()));
+  HIP_TRY(upl(ca.scope_name, scope_name.data(), 8 * S));
+  HIP_TRY(upl(ca.scope_has, scope_has.data(), K * S));
+  HIP_TRY(upl(ca.scope_val, scope_val.data(), 8 * K * S));
+  HIP_TRY(upl(ca.res_has, res_has.data(), K * R));
+  HIP_TRY(upl(ca.res_val, res_val.data(), 8 * K * R));
+  if (cnt && K) {
+    const size_t hb = up(K * cnt + 16), vb = up(8 * K * cnt + 16), kb = up(4 * K * cnt + 16);
+    if ((rc = b->cafix.need(hb + vb + kb))) return rc;
+    HIP_TRY(upl(b->cafix.p, fix_has.data(), K * cnt));
+    HIP_TRY(upl(b->cafix.p + hb, fix_val.data(), 8 * K * cnt));
+    HIP_TRY(upl(b->cafix.p + hb + vb, fix_kv.data(), 4 * K * cnt));
+    OtlpCondAttrFixArgs fa{};
+    fa.cnt = (uint32_t)cnt;
+    fa.n_keys = (uint32_t)K;
+    fa.n_spans = n;
+    fa.list = host_list;
+    fa.fix_has = b->cafix.p;
+    fa.fix_val = reinterpret_cast<const ose_strref*>(b->cafix.p + hb);
+    fa.fix_kv = reinterpret_cast<const uint32_t*>(b->cafix.p + hb + vb);
+    fa.span_has = const_cast<uint8_t*>(ca.span_has);
+    fa.span_val = const_cast<ose_strref*>(ca.span_val);
+    fa.span_kv_size = const_cast<uint32_t*>(ca.span_kv_size);
+    launch_otlp_condattr_fix(fa, st);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipStreamSynchronize(st));   // the sources are on this stack
+  c.arena_bytes = end;
+  ca.n_spans = n;
+  ca.n_resources = (uint32_t)R;
+  ca.n_scopes = (uint32_t)S;
+  ca.arena_bytes = end;
+  ca.arena = c.arena;
+  ca.scope = c.scope;
+  ca.scope_resource = c.scope_resource;
+  ca.span_size = c.span_size;
+  b->ca_on = true;
+  return 0;
+}
+
 int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchImpl* b, bool host_scopes = false,
            bool host_res = false) {
   int rc;
@@ -1236,6 +1515,9 @@ int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchIm
     if (k != 4 && k != 5) b->walk_info[k] = 0;   // (the redo flags are the outer call's)
   // engine option otlp_sqlop: db_flags / db_query / res_sql_ok are decoded too
   const bool sql = e->has_sqlop && e->option(Engine::kOptOtlpSqlop);
+  // engine option otlp_condattr: odigosconditionalattributes' columns are decoded too
+  const bool ca = e->has_condattr && e->option(Engine::kOptOtlpCondattr);
+  b->ca_on = false;
   // 1. the bytes H2D (straight from the caller's buffer when it is pinned,
   //    else through pinned staging), the walk meanwhile
   const size_t pb_cap = up(len + 16, 16);
@@ -1458,13 +1740,14 @@ int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchIm
     HIP_TRY(hipGetLastError());
     e->prof_end(tq, st);
   }
+  if (ca && (rc = condattr_spans(e, b, n, span_ref, host_flag, host_count, host_list, st))) return rc;
   // 4. the host pass
   uint32_t cnt = 0;
   HIP_TRY(hipMemcpyAsync(&cnt, host_count, 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   b->host_spans = cnt;
   lap(3);
-  if (!cnt) return 0;
+  if (!cnt) return ca ? condattr_finish(e, b, pb, {}, host_list, st) : 0;
   std::vector<uint32_t> span_res;
   const std::vector<uint32_t>* sres = &w.span_res;
   if (gpu_res && !o->wide_host_rules) {   // the resources' span_attribute service bits from the device
@@ -1602,6 +1885,7 @@ int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchIm
     HIP_TRY(hipGetLastError());
   }
   HIP_TRY(hipStreamSynchronize(st));   // fixdev and the staging are reused / freed
+  if (ca && (rc = condattr_finish(e, b, pb, list, host_list, st))) return rc;
   lap(4);
   return 0;
 }
@@ -1611,11 +1895,19 @@ int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchIm
 namespace {
 // 0 with *host false: *o holds the outputs; 0 with *host true: the host
 // encoder takes the call (o->fallback says why); else an error code
+// ca (ose_otlp_encode_condattr; sampled, tmpl and sql false): odigosconditionalattributes'
+// puts are applied, by the kernels' instances for them.
 int encode_gpu(OtlpBatchImpl* b, const ose_outputs* outs, bool sampled, bool tmpl, bool sql, const Router* router,
-               hipStream_t st, OtlpOut* o, bool* host, std::vector<uint64_t>* res_off = nullptr) {
+               hipStream_t st, OtlpOut* o, bool* host, std::vector<uint64_t>* res_off = nullptr,
+               const ose_condattr_outputs* ca = nullptr) {
   *host = true;
   if (b->e->option(Engine::kOptEncodeHost)) return 0;   // engine option encode_host: the host encoder always
   if (router && router->pipelines.size() > 63) return 0;   // the host encoder reports it
+  const uint32_t ca_T = ca ? (uint32_t)b->e->condattr_tab.target_key.size() : 0;
+  if (ca_T > kEncCaTargets) {   // the host encoder has no bound on the targets
+    o->fallback = kEncFbCa;
+    return 0;
+  }
   const uint64_t n = b->cols.n_spans, S = b->cols.n_scopes, R = b->cols.n_resources;
   if (!b->d_spans) return 0;
   const uint32_t n_out = router ? (uint32_t)router->pipelines.size() + 1 : 1;
@@ -1645,6 +1937,12 @@ int encode_gpu(OtlpBatchImpl* b, const ose_outputs* outs, bool sampled, bool tmp
   };
   if (tmpl || sql) parts.push_back({(void**)&a.edit, sizeof(EncEdit) * n});
   if (sql) parts.push_back({(void**)&a.sql_edit, sizeof(EncSqlEdit) * n});
+  EncCaArgs ca_a{};
+  if (ca) {   // the puts in the workspace (src / val may be host memory), and the new span lengths
+    parts.push_back({(void**)&ca_a.ca_src, (size_t)ca_T * n});
+    parts.push_back({(void**)&ca_a.ca_val, 8 * (size_t)ca_T * n});
+    parts.push_back({(void**)&ca_a.ca_len, 4 * n});
+  }
   if (blob) parts.push_back({(void**)&routes, blob});
   // the layout arrays the decoder left on the host go up
   const bool up_scopes = !b->scopes_dev, up_res = !b->res_on_device;
@@ -1727,7 +2025,20 @@ int encode_gpu(OtlpBatchImpl* b, const ose_outputs* outs, bool sampled, bool tmp
   auto t0 = clk::now();
   // sizing pass, offsets
   HIP_TRY(hipMemsetAsync(flags64, 0, 8, st));
-  launch_enc_spans(a, st);
+  if (ca) {
+    if ((uint64_t)ca_T * n) {
+      HIP_TRY(hipMemcpyAsync(const_cast<uint8_t*>(ca_a.ca_src), ca->src, (size_t)ca_T * n, hipMemcpyDefault, st));
+      HIP_TRY(hipMemcpyAsync(const_cast<ose_strref*>(ca_a.ca_val), ca->val, 8 * (size_t)ca_T * n, hipMemcpyDefault, st));
+    }
+    static_cast<EncArgs&>(ca_a) = a;
+    ca_a.ca_blob = b->e->condattr_blob_dev;
+    ca_a.ca_targets = ca_T;
+    ca_a.ca_string_bytes = b->e->condattr_tab.string_bytes;
+    ca_a.ca_arena_bytes = b->cols.arena_bytes;
+    launch_enc_spans_ca(ca_a, st);
+  } else {
+    launch_enc_spans(a, st);
+  }
   HIP_TRY(hipGetLastError());
   launch_enc_scopes(a, st);
   HIP_TRY(hipGetLastError());
@@ -1770,7 +2081,12 @@ int encode_gpu(OtlpBatchImpl* b, const ose_outputs* outs, bool sampled, bool tmp
   if (oom) return fail(OSE_EDEVICE, "out of pinned host memory for the encoder outputs");
   o->t_ms[2] = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
   t0 = clk::now();
-  launch_enc_write(a, st);
+  if (ca) {
+    static_cast<EncArgs&>(ca_a) = a;   // (a.out is set by now)
+    launch_enc_write_ca(ca_a, st);
+  } else {
+    launch_enc_write(a, st);
+  }
   HIP_TRY(hipGetLastError());
   for (uint32_t k = 0; k < n_out; k++)
     if (tot[k]) HIP_TRY(hipMemcpyAsync(o->outs[k].data, a.out + base[k], tot[k], hipMemcpyDeviceToHost, st));
@@ -2171,6 +2487,130 @@ int ose_otlp_encode(ose_engine* eng, const ose_otlp_batch* bb, const ose_outputs
   return 0;
 }
 
+const ose_condattr_columns* ose_otlp_condattr_columns(const ose_otlp_batch* bb) {
+  if (!bb) return nullptr;
+  const auto* b = reinterpret_cast<const OtlpBatchImpl*>(bb);
+  return b->ca_on && !b->released ? &b->ca : nullptr;
+}
+
+int ose_otlp_condattr_download(const ose_otlp_batch* bb, const ose_condattr_columns* dst) {
+  if (!bb || !dst) return fail(OSE_EINVAL, "NULL argument");
+  const auto* b = reinterpret_cast<const OtlpBatchImpl*>(bb);
+  if (!b->ca_on || b->released)
+    return fail(OSE_EINVAL, "ose_otlp_condattr_download: the batch was decoded with the engine option otlp_condattr off");
+  if (int rc = bind_device(b->e)) return rc;
+  const ose_condattr_columns& c = b->ca;
+  const uint64_t n = c.n_spans, R = c.n_resources, S = c.n_scopes, K = b->ca_keys;
+  struct F { const void* src; const void* dst; size_t bytes; };
+  const F fs[] = {
+      {c.arena, dst->arena, c.arena_bytes}, {c.scope, dst->scope, 4 * n}, {c.scope_resource, dst->scope_resource, 4 * S},
+      {c.scope_name, dst->scope_name, 8 * S}, {c.span_has, dst->span_has, K * n}, {c.span_val, dst->span_val, 8 * K * n},
+      {c.span_kv_size, dst->span_kv_size, 4 * K * n}, {c.scope_has, dst->scope_has, K * S},
+      {c.scope_val, dst->scope_val, 8 * K * S}, {c.res_has, dst->res_has, K * R}, {c.res_val, dst->res_val, 8 * K * R},
+      {c.span_size, dst->span_size, 4 * n},
+  };
+  for (auto& f : fs)
+    if (f.src && f.dst && f.bytes) HIP_TRY(hipMemcpy(const_cast<void*>(f.dst), f.src, f.bytes, hipMemcpyDefault));
+  return 0;
+}
+
+int ose_otlp_encode_condattr(ose_engine* eng, const ose_otlp_batch* bb, const ose_condattr_outputs* ca,
+                             const ose_router* router, void* hip_stream, ose_otlp_out** out) {
+  if (!eng || !bb || !out) return fail(OSE_EINVAL, "NULL argument");
+  Engine* e = reinterpret_cast<Engine*>(eng);
+  if (!(e->has_condattr && e->option(Engine::kOptOtlpCondattr)))
+    return fail(OSE_ENOTSUP, "ose_otlp_encode_condattr: the engine option otlp_condattr is off");
+  auto* b = const_cast<OtlpBatchImpl*>(reinterpret_cast<const OtlpBatchImpl*>(bb));
+  if (b->released) return fail(OSE_EINVAL, "ose_otlp_encode_condattr does not take a batch released by a groupbytrace store");
+  if (b->e != e) return fail(OSE_EINVAL, "the batch belongs to another engine");
+  if (!b->ca_on) return fail(OSE_EINVAL, "the batch was decoded with the engine option otlp_condattr off");
+  const CondAttrCompiled& tab = e->condattr_tab;
+  const uint64_t n = b->cols.n_spans;
+  const uint32_t T = (uint32_t)tab.target_key.size();
+  if (!ca || ((uint64_t)T * n && (!ca->src || !ca->val))) return fail(OSE_EINVAL, "src or val is NULL");
+  if (int rc = bind_device(e)) return rc;
+  hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  const auto t_start = std::chrono::steady_clock::now();
+  uint32_t gpu_fallback = 0;
+  {   // the GPU encoder
+    auto* o = new OtlpOut();
+    o->e = e;
+    engine_retain(e);   // dropped by otlp_out_release
+    {
+      std::lock_guard<std::mutex> g(e->mu);
+      if (!e->enc_pool.empty()) {
+        o->work = static_cast<EncodeWork*>(e->enc_pool.back());
+        e->enc_pool.pop_back();
+      }
+    }
+    if (!o->work) o->work = encode_work_new();
+    bool host = true;
+    const int rc = encode_gpu(b, nullptr, false, false, false, reinterpret_cast<const Router*>(router), st, o, &host, nullptr, ca);
+    if (rc || host) {
+      gpu_fallback = o->fallback;
+      otlp_out_release(o);
+      if (rc) return rc;
+    } else {
+      *out = reinterpret_cast<ose_otlp_out*>(o);
+      return 0;
+    }
+  }
+  // the host encoder: the puts, the decoder's span sizes and what the decode
+  // put behind the message bytes, D2H into the batch's pinned staging
+  const uint64_t tail_base = std::min<uint64_t>(b->pb_len, b->cols.arena_bytes), tail = b->cols.arena_bytes - tail_base;
+  const size_t o_src = 0, o_val = up((size_t)T * n + 16), o_size = o_val + up(8 * (size_t)T * n + 16),
+               o_tail = o_size + up(4 * n + 16), o_end = o_tail + up(tail + 16);
+  int rc;
+  if ((rc = b->stage.need(o_end))) return rc;
+  uint8_t* h = b->stage.p;
+  if ((uint64_t)T * n) {
+    HIP_TRY(hipMemcpyAsync(h + o_src, ca->src, (size_t)T * n, hipMemcpyDefault, st));
+    HIP_TRY(hipMemcpyAsync(h + o_val, ca->val, 8 * (size_t)T * n, hipMemcpyDefault, st));
+  }
+  if (n) HIP_TRY(hipMemcpyAsync(h + o_size, b->cols.span_size, 4 * n, hipMemcpyDeviceToHost, st));
+  if (tail) HIP_TRY(hipMemcpyAsync(h + o_tail, b->arena.p + tail_base, tail, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  std::string err;
+  if ((rc = condattr_check_puts(h + o_src, reinterpret_cast<const ose_strref*>(h + o_val), n, T, b->cols.arena_bytes,
+                                tab.string_bytes, err)))
+    return fail(rc, err);
+  std::vector<std::string> names(T);
+  for (uint32_t u = 0; u < T; u++) names[u] = tab.keys[tab.target_key[u]];
+  EncodeDecisions d;
+  d.span_size = reinterpret_cast<const uint32_t*>(h + o_size);
+  if ((uint64_t)T * n) {
+    d.ca_src = h + o_src;
+    d.ca_val = reinterpret_cast<const ose_strref*>(h + o_val);
+    d.ca_targets = T;
+    d.ca_names = names.data();
+    d.ca_arena = b->pb;
+    d.ca_tail_base = tail_base;
+    d.ca_tail = h + o_tail;
+    d.ca_strings = tab.blob.data() + tab.strings_off;
+  }
+  if ((rc = layout_to_host(b, st))) return rc;
+  auto* o = new OtlpOut();
+  o->e = e;
+  engine_retain(e);   // dropped by otlp_out_release
+  {
+    std::lock_guard<std::mutex> g(e->mu);
+    if (!e->enc_pool.empty()) {
+      o->work = static_cast<EncodeWork*>(e->enc_pool.back());
+      e->enc_pool.pop_back();
+    }
+  }
+  if (!o->work) o->work = encode_work_new();
+  o->fallback = gpu_fallback;
+  o->t_ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+  if (!encode_traces(b->pb, b->pb_len, b->span_ref, b->lay, d, reinterpret_cast<const Router*>(router), encode_threads(),
+                     *o->work, o->outs, err, o->t_ms + 1)) {
+    otlp_out_release(o);
+    return fail(OSE_EINVAL, err);
+  }
+  *out = reinterpret_cast<ose_otlp_out*>(o);
+  return 0;
+}
+
 // Test seam (CPU): the encoder on the host walk of `pb` with the given
 // decisions (keep / url_out / tmpl NULL when absent) and span sizes
 // computed on the host as the decoder would.  sql_op: OSE_SQLOP_* per span
@@ -2218,6 +2658,58 @@ int osehost_otlp_encode(const uint8_t* pb, size_t len, const uint8_t* keep, int 
                         const ose_router* router, int threads, ose_otlp_out** out) {
   return osehost_otlp_encode_sql(pb, len, keep, drop_all, url_out, tmpl, tmpl_arena, tmpl_arena_len, router, threads, out,
                                  nullptr);
+}
+
+// Test seam (CPU): the host encoder applying odigosconditionalattributes' puts
+// (what ose_otlp_encode_condattr's host path runs) on the host walk of `pb`.
+// src / val: [n_targets * n_spans] as ose_condattr_outputs, host memory;
+// arena: the bytes OSE_CA_ARENA values point into; strings: the string table
+// of OSE_CA_CONFIG values; names: the target names' bytes back to back, their
+// lengths in name_lens.  n_spans other than the message's is OSE_EINVAL; src
+// and val are checked as ose_otlp_encode_condattr checks them.
+int osehost_otlp_encode_condattr(const uint8_t* pb, size_t len, uint64_t n_spans, const uint8_t* src,
+                                 const ose_strref* val, uint32_t n_targets, const uint8_t* arena, uint64_t arena_bytes,
+                                 const uint8_t* strings, uint64_t string_bytes, const uint8_t* names,
+                                 const uint32_t* name_lens, const ose_router* router, int threads, ose_otlp_out** out) {
+  if ((!pb && len) || !out) return fail(OSE_EINVAL, "NULL argument");
+  if (n_targets && n_spans && (!src || !val)) return fail(OSE_EINVAL, "src or val is NULL");
+  if (n_targets && !name_lens) return fail(OSE_EINVAL, "NULL argument");
+  ColumnizeCtx ctx;
+  std::string err = ctx.build(nullptr, nullptr, nullptr);
+  Walked w;
+  ResCache cache;
+  if (err.empty() && !walk(ctx, cache, pb, len, w)) err = w.err;
+  if (!err.empty()) return fail(OSE_EINVAL, err);
+  if (w.span_ref.size() != n_spans) return fail(OSE_EINVAL, "n_spans is not the message's span count");
+  if (int rc = condattr_check_puts(src, val, n_spans, n_targets, arena_bytes, string_bytes, err)) return fail(rc, err);
+  std::vector<uint32_t> sizes(w.span_ref.size());
+  ProtoSizer sizer;
+  for (size_t i = 0; i < sizes.size(); i++) {
+    Span sp;
+    if (!pb_span(pb + (uint32_t)w.span_ref[i], (size_t)(w.span_ref[i] >> 32), sp))
+      return fail(OSE_EINVAL, "OTLP protobuf: malformed Span");
+    sizes[i] = (uint32_t)sizer.span(sp);
+  }
+  std::vector<std::string> target_names(n_targets);
+  for (uint32_t u = 0, at = 0; u < n_targets; at += name_lens[u], u++)
+    target_names[u].assign(reinterpret_cast<const char*>(names) + at, name_lens[u]);
+  EncodeDecisions d;
+  d.span_size = sizes.data();
+  d.ca_src = src;
+  d.ca_val = val;
+  d.ca_targets = n_targets;
+  d.ca_names = target_names.data();
+  d.ca_arena = arena;
+  d.ca_strings = strings;
+  auto* o = new OtlpOut();
+  o->work = encode_work_new();
+  if (!encode_traces(pb, len, w.span_ref, w.lay, d, reinterpret_cast<const Router*>(router),
+                     threads > 0 ? threads : encode_threads(), *o->work, o->outs, err, o->t_ms + 1)) {
+    otlp_out_release(o);
+    return fail(OSE_EINVAL, err);
+  }
+  *out = reinterpret_cast<ose_otlp_out*>(o);
+  return 0;
 }
 
 void ose_otlp_release(ose_otlp_batch* bb) {

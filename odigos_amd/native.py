@@ -218,6 +218,9 @@ def lib() -> C.CDLL:
         "ose_condattr_scratch_words": (C.c_uint64, [_p, C.c_uint32]),
         "ose_condattr_process_device": (C.c_int, [_p, C.POINTER(CondAttrColumns), C.POINTER(CondAttrOutputs), _p]),
         "ose_condattr_process": (C.c_int, [_p, C.POINTER(CondAttrColumns), C.POINTER(CondAttrOutputs)]),
+        "ose_otlp_condattr_columns": (C.POINTER(CondAttrColumns), [_p]),
+        "ose_otlp_condattr_download": (C.c_int, [_p, C.POINTER(CondAttrColumns)]),
+        "ose_otlp_encode_condattr": (C.c_int, [_p, _p, C.POINTER(CondAttrOutputs), _p, _p, C.POINTER(_p)]),
         "ose_profile_enable": (C.c_int, [_p, C.c_int]),
         "ose_profile_read": (C.c_int, [_p, C.c_char_p, C.c_size_t]),
         # host layer (odigos_amd/csrc/host.cpp)
@@ -251,6 +254,10 @@ def lib() -> C.CDLL:
         # ... plus sql_op (odigossqldboperationprocessor's decisions, NULL when absent)
         "osehost_otlp_encode_sql": (C.c_int, [C.c_char_p, C.c_size_t, _p, C.c_int, _p, _p, _p, C.c_uint64, _p, C.c_int,
                                               C.POINTER(_p), _p]),
+        # odigosconditionalattributes' puts: pb, len, n_spans, src, val, n_targets, arena, arena_bytes, strings,
+        # string_bytes, names, name_lens, router, threads, out
+        "osehost_otlp_encode_condattr": (C.c_int, [C.c_char_p, C.c_size_t, C.c_uint64, _p, _p, C.c_uint32, _p, C.c_uint64,
+                                                   _p, C.c_uint64, _p, _p, _p, C.c_int, C.POINTER(_p)]),
         "osehost_router_create_signal": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(_p)]),
         "osehost_router_route": (_p, [_p, C.c_char_p]),
         "osehost_router_table": (C.c_int, [_p, _p, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),

@@ -17,6 +17,21 @@ has the odigossqldboperationprocessor section and the engine option
 otlp_sqlop on, the stages include SQLOP, and a third of the spans carry a
 db.query.text (as in tools/sqlop_bench.py).  The decoder's second pass
 (otlp_sqlop_kernel) is reported as a row of its own, with its roofline.
+
+--condattr: the node collector's pipeline instead: an engine
+with the shipped category-attributes profile
+(tests/golden/category_attributes_profile.json) and odigostrafficmetrics only,
+engine option otlp_condattr on; the resources' scope names are drawn from the
+profile's 269 values and 30 names outside them.  ose_otlp_decode ->
+ose_condattr_process_device on the decoded columns -> SIZE with span_size_out
+-> ose_otlp_encode_condattr, each leg timed; otlp_condattr_kernel by HIP
+events, its bytes (the message read again, span_ref and the host flag read,
+the hits' columns written) against osehost_stream_copy in the same process;
+the same at 8192-span requests (one caller with each leg timed; 8 callers for
+whole-job spans/s only: their legs overlap and are not reported).  Writes
+profiles/otlp_condattr_bench.json unless --out names another file; an
+"option_off_ab" entry already in that file (the parent-commit comparison,
+made by a job of its own) is kept.  A record, not a gate.
 """
 from __future__ import annotations
 
@@ -35,8 +50,13 @@ def main():
     ap.add_argument("--spans", type=int, default=10_000_000)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--sqlop", action="store_true", help="odigossqldboperationprocessor through the OTLP path")
+    ap.add_argument("--condattr", action="store_true", help="odigosconditionalattributes through the OTLP path")
     ap.add_argument("--out", default=str(ROOT / "gpurun_out" / "otlp.json"))
     args = ap.parse_args()
+    if args.condattr:
+        if args.out == ap.get_default("out"):
+            args.out = str(ROOT / "profiles" / "otlp_condattr_bench.json")
+        return condattr_main(args)
     if args.sqlop and args.out == ap.get_default("out"):   # a file of its own beside the default
         args.out = str(Path(args.out).with_name("otlp_sqlop.json"))
     sql_every = 3 if args.sqlop else 0
@@ -265,6 +285,178 @@ def main():
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
     Path(args.out).write_text(line + "\n")
     print(line, flush=True)
+
+
+def condattr_main(args):
+    import ctypes as C
+
+    import torch
+    from bench import cpu_share
+    from odigos_amd import native
+    from odigos_amd.batch import Engine, Generator, OtlpBatch, PinnedBuffer, Router, device_outputs
+    share, nproc, model = cpu_share()
+    threads = max(1, min(16, share))
+    # the shipped profile as the processor's config (action lists shared by name in the file)
+    prof_json = json.loads((ROOT / "tests" / "golden" / "category_attributes_profile.json").read_text())
+    cfg = {"global_default": prof_json["global_default"],
+           "rules": [{"field_to_check": r["field_to_check"],
+                      "new_attribute_value_configurations": {v: r["action_lists"][k] for v, k in r["values"].items()}}
+                     for r in prof_json["rules"]]}
+    SECTION, TRAFFIC = "odigosconditionalattributes", {"res_attributes_keys": ["service.name", "k8s.namespace.name"]}
+    names = list(cfg["rules"][0]["new_attribute_value_configurations"]) + ["unknown.library.%d" % k for k in range(30)]
+    eng = Engine({SECTION: cfg, "odigostrafficmetrics": TRAFFIC})
+    eng.set_option("otlp_condattr", 1)
+    L = eng.L
+    info = eng.condattr_info()
+    T, K = info.n_targets, info.n_keys
+    sh = torch.cuda.current_stream().cuda_stream
+    streams = [{"name": "ds-a", "sources": [{"namespace": "default", "kind": "Deployment", "name": "svc-%02d" % k}
+                                            for k in range(0, 12)],
+                "destinations": [{"destinationname": "d1", "configuredsignals": ["TRACES"]}]}]
+    router = Router({"datastreams": streams})
+    res = {"metric": "OTLP protobuf ingest: host TracesData bytes -> decoded columns -> CONDATTR -> SIZE -> "
+                     "ose_otlp_encode_condattr (the category-attributes profile)",
+           "condattr": True, "targets": T, "keys": K, "scope_names": len(names), "host_cpu": model, "cpu_share": share,
+           "nproc": nproc}
+
+    def setup(n_spans, seed):
+        g = Generator("fused", seed=seed, n_spans=n_spans, threads=threads)
+        pb = g.otlp(threads, scope_names=names)
+        dims = native.Columns()
+        dims.n_spans, dims.n_resources, dims.n_attrsets = n_spans, g.cols.n_resources, 4096
+        outs = device_outputs(dims, tmpl_cap=16)
+        words = int(L.ose_condattr_scratch_words(eng.h, g.cols.n_resources))
+        z = lambda nb: torch.zeros(max(16, nb), dtype=torch.uint8, device="cuda")   # noqa: E731
+        t = {"src": z(T * n_spans), "val": z(8 * T * n_spans), "span_size_out": z(4 * n_spans), "scratch": z(4 * words),
+             "device_status": z(16)}
+        o = native.CondAttrOutputs()
+        for k, v in t.items():
+            setattr(o, k, v.data_ptr())
+        return pb, PinnedBuffer(pb), outs, o, t
+
+    def one(pin, outs, o, stream):
+        a = time.perf_counter()
+        ob = OtlpBatch(eng, pin.p, stream=stream, length=pin.n, outputs=outs)
+        b = time.perf_counter()
+        native.check(L.ose_condattr_process_device(eng.h, C.byref(ob.condattr_cols), C.byref(o), C.c_void_p(stream)))
+        ob.cols.span_size = o.span_size_out
+        eng.process_device(ob, native.STAGE_SIZE, native.GROUP_TRACE_ID, stream=stream)
+        torch.cuda.synchronize() if stream == sh else None
+        c = time.perf_counter()
+        path = {}
+        out = eng.otlp_encode_condattr(ob, o, router, stream=stream, copy=False, path=path)
+        d = time.perf_counter()
+        r = {"decode": (b - a) * 1e3, "stages": (c - b) * 1e3, "encode": (d - c) * 1e3, "phases": ob.timings_ms,
+             "host_spans": ob.host_spans, "path": path, "out": out, "arena_bytes": ob.cols.arena_bytes}
+        ob.close()
+        return r
+
+    t0 = time.perf_counter()
+    pb, pin, outs, o, keep = setup(args.spans, 0x0D16F0A1)
+    print(f"generated {len(pb) / 1e9:.2f} GB for {args.spans} spans in {time.perf_counter() - t0:.1f}s", flush=True)
+    res.update({"spans": args.spans, "message_bytes": len(pb), "bytes_per_span": len(pb) / args.spans})
+    for _ in range(2):
+        one(pin, outs, o, sh)
+    eng.profile(True)
+    runs = [one(pin, outs, o, sh) for _ in range(args.reps)]
+    prof = eng.profile_read()
+    eng.profile(False)
+    best = min(runs, key=lambda r: r["decode"] + r["stages"] + r["encode"])
+    puts = int((keep["src"][:T * args.spans] != 0).sum().item())
+    res["decode_pinned_ms"] = best["decode"]
+    res["decode_phases_ms"] = best["phases"]
+    res["stages_ms"] = best["stages"]
+    res["encode_ms"] = best["encode"]
+    res["encode_path"] = best["path"]
+    res["encode_outputs"] = [{"pipeline": p, "bytes": nb, "resources": nr} for p, nb, nr in best["out"]]
+    res["host_pass_spans"] = best["host_spans"]
+    res["puts"] = puts
+    res["end_to_end_spans_per_s"] = args.spans / ((best["decode"] + best["stages"] + best["encode"]) * 1e-3)
+    res["kernels_ms_per_call"] = {k: v["ms"] / max(v["launches"], 1) for k, v in prof.items()}
+    # otlp_condattr_kernel: the message bytes read again, span_ref (8) and the host flag (1) per span read, and
+    # per hit has (1) + val (8) + kv_size (4, target keys) written; the hits counted from the decoded columns
+    ob = OtlpBatch(eng, pin.p, stream=sh, length=pin.n, outputs=outs)
+    hits = int(np_sum_has(ob, K))
+    ob.close()
+    k_ms = res["kernels_ms_per_call"].get("otlp_condattr_kernel", 0.0)
+    alg = len(pb) + 9 * args.spans + 13 * hits
+    bw = C.c_double()
+    a_ = torch.empty(1 << 30, dtype=torch.uint8, device="cuda")
+    b_ = torch.empty(1 << 30, dtype=torch.uint8, device="cuda")
+    native.check(L.osehost_stream_copy(b_.data_ptr(), a_.data_ptr(), a_.numel(), 10, C.c_void_p(sh), C.byref(bw)))
+    del a_, b_
+    res["otlp_condattr_kernel"] = {"ms": k_ms, "span_has_hits": hits, "algorithmic_bytes": alg,
+                                   "algorithmic_gbs": alg / (k_ms * 1e-3) / 1e9 if k_ms else 0.0, "stream_copy_gbs": bw.value}
+    res["otlp_condattr_kernel"]["frac_of_stream_copy"] = (res["otlp_condattr_kernel"]["algorithmic_gbs"] / bw.value
+                                                          if bw.value else 0.0)
+    pin.close()
+    # 8192-span requests: one caller's latency, then 8 callers
+    spb, spin, souts, so, skeep = setup(8192, 0x0D16F0A2)
+    lat = []
+    for k in range(220):
+        a = time.perf_counter()
+        r = one(spin, souts, so, sh)
+        if k >= 20:
+            lat.append((time.perf_counter() - a, r["decode"], r["stages"], r["encode"]))
+    lat.sort()
+    med = lambda j: sorted(x[j] for x in lat)[len(lat) // 2]   # noqa: E731
+    res["batch8192_us"] = {"p50": med(0) * 1e6, "p99": lat[int(len(lat) * 0.99)][0] * 1e6}
+    res["batch8192_legs_ms_median"] = {"decode": med(1), "stages": med(2), "encode": med(3)}
+    res["batch8192_spans_per_s"] = 8192 / med(0)
+    res["batch8192_encode_path"] = r["path"]
+    import threading
+    callers, per = 8, 120
+    ready = threading.Barrier(callers + 1)
+    errs = []
+
+    def caller(k):
+        try:
+            cs = torch.cuda.Stream()
+            _, _, co, cobj, ckeep = setup(8192, 0x0D16F0A2)
+            ready.wait()
+            for _ in range(per):
+                one(spin, co, cobj, cs.cuda_stream)
+            cs.synchronize()
+        except Exception as ex:   # pragma: no cover
+            errs.append(repr(ex))
+            ready.abort()
+
+    th = [threading.Thread(target=caller, args=(k,)) for k in range(callers)]
+    for t_ in th:
+        t_.start()
+    ready.wait()
+    a = time.perf_counter()
+    for t_ in th:
+        t_.join()
+    wall = time.perf_counter() - a
+    assert not errs, errs
+    res["batch8192_callers"] = {"callers": callers, "calls": callers * per, "wall_s": wall,
+                                "spans_per_s": callers * per * 8192 / wall}
+    spin.close()
+    out = Path(args.out)
+    if out.exists():
+        try:
+            old = json.loads(out.read_text())
+            if "option_off_ab" in old:
+                res["option_off_ab"] = old["option_off_ab"]
+        except ValueError:
+            pass
+    out.parent.mkdir(parents=True, exist_ok=True)
+    out.write_text(json.dumps(res, indent=1) + "\n")
+    print(json.dumps(res), flush=True)
+
+
+def np_sum_has(ob, K):
+    """span_has entries set in a decoded batch's odigosconditionalattributes columns."""
+    import ctypes as C
+
+    import numpy as np
+    from odigos_amd import native
+    has = np.zeros(K * ob.cols.n_spans + 16, dtype=np.uint8)
+    dst = native.CondAttrColumns()
+    dst.span_has = has.ctypes.data
+    native.check(ob.L.ose_otlp_condattr_download(ob.h, C.byref(dst)))
+    return has.sum(dtype="uint64")
 
 
 if __name__ == "__main__":
