@@ -11,12 +11,6 @@
 
 namespace ose {
 
-#define HIP_TRY(expr)                                                                                  \
-  do {                                                                                                 \
-    hipError_t _e = (expr);                                                                            \
-    if (_e != hipSuccess) return fail(OSE_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
 namespace {
 uint32_t op_code(const std::string& cond, const std::string& op) {
   if (op == "exists") return kAttrOpExists;

@@ -23,12 +23,6 @@
 
 namespace ose {
 
-#define HIP_TRY(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t _e = (expr);                                                             \
-    if (_e != hipSuccess) return fail(OSE_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
 namespace {
 constexpr size_t kAlign = 256;
 constexpr size_t kPoolMax = 64;                    // pooled batches per engine

@@ -14,12 +14,6 @@
 
 namespace ose {
 
-#define HIP_TRY(expr)                                                                                  \
-  do {                                                                                                 \
-    hipError_t _e = (expr);                                                                            \
-    if (_e != hipSuccess) return fail(OSE_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
 namespace {
 size_t up16(size_t x) { return (x + 15) / 16 * 16; }
 }  // namespace

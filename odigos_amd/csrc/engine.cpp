@@ -29,12 +29,6 @@ int fail(int code, const std::string& msg) {
   return code;
 }
 
-#define HIP_TRY(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t _e = (expr);                                                             \
-    if (_e != hipSuccess) return fail(OSE_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
 // odigosurltemplate tables: newUrlTemplateProcessor (processor.go:27-69)
 // groups rules by segment count keeping config order; custom ids default
 // their name to "id".

@@ -17,6 +17,12 @@
 namespace ose {
 
 int fail(int code, const std::string& msg);
+// a HIP call whose failure ends the enclosing function with OSE_EDEVICE
+#define HIP_TRY(expr)                                                                                  \
+  do {                                                                                                 \
+    hipError_t _e = (expr);                                                                            \
+    if (_e != hipSuccess) return fail(OSE_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); \
+  } while (0)
 struct Engine;
 // makes the engine's device current on the calling thread (a shim's
 // goroutines migrate across OS threads; HIP's current device is per thread)
@@ -53,7 +59,8 @@ void release_condattr(Engine* e);                  // condattr_host.cpp
 int build_condattr_keytab(Engine* e);              // condattr_host.cpp (engine option otlp_condattr)
 
 // What the groupbytrace store (gbt_host.cpp) reads of a decoded ose_otlp_batch
-// and writes into the one it releases (otlp_host.cpp owns the type).
+// and writes into the one it releases (the type is otlp_batch.hpp's; these
+// are otlp_host.cpp's, the encode of a released batch otlp_encode_host.cpp's).
 struct OtlpBatchView {
   Engine* e;
   const ose_columns* cols;

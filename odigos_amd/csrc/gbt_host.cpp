@@ -32,12 +32,6 @@
 
 namespace ose {
 
-#define HIP_TRY(expr)                                                                                  \
-  do {                                                                                                 \
-    hipError_t _e = (expr);                                                                            \
-    if (_e != hipSuccess) return fail(OSE_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
 namespace {
 size_t up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 

@@ -1,4 +1,6 @@
-// otlp_host.cpp — OTLP protobuf ingest: ose_otlp_*.
+// otlp_host.cpp — OTLP protobuf ingest: ose_otlp_decode, the
+// batch's accessors and its release.  The batch type is in otlp_batch.hpp; the
+// way back to bytes (ose_otlp_encode*) is otlp_encode_host.cpp.
 //
 // One call turns a serialized TracesData into device columns:
 //   1. the bytes go to pinned staging and H2D (the arena: strings are
@@ -31,41 +33,24 @@
 #include "columnize.hpp"
 #include "engine_internal.hpp"
 #include "kernels.hpp"
+#include "otlp_batch.hpp"
 #include "otlp_encode.hpp"
 #include "otlp_pb.hpp"
 #include "taskpool.hpp"
 
 namespace ose {
 
-#define HIP_TRY(expr)                                                                                  \
-  do {                                                                                                 \
-    hipError_t _e = (expr);                                                                            \
-    if (_e != hipSuccess) return fail(OSE_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
-namespace {
-size_t up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
-
-struct DevBuf {   // grow-only device (or pinned host) buffer
-  uint8_t* p = nullptr;
-  size_t cap = 0;
-  bool host = false;
-  int need(size_t bytes) {
-    if (bytes <= cap) return 0;
-    if (p) { if (host) (void)hipHostFree(p); else (void)hipFree(p); }
-    p = nullptr;
-    cap = 0;
-    const size_t want = up(std::max<size_t>(bytes + bytes / 4, 1 << 20), 1 << 16);
-    if (host) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&p), want, hipHostMallocDefault));
-    else HIP_TRY(hipMalloc(reinterpret_cast<void**>(&p), want));
-    cap = want;
-    return 0;
-  }
-  ~DevBuf() {
-    if (p) { if (host) (void)hipHostFree(p); else (void)hipFree(p); }
-  }
-};
-}  // namespace
+int DevBuf::need(size_t bytes) {
+  if (bytes <= cap) return 0;
+  if (p) { if (host) (void)hipHostFree(p); else (void)hipFree(p); }
+  p = nullptr;
+  cap = 0;
+  const size_t want = up(std::max<size_t>(bytes + bytes / 4, 1 << 20), 1 << 16);
+  if (host) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&p), want, hipHostMallocDefault));
+  else HIP_TRY(hipMalloc(reinterpret_cast<void**>(&p), want));
+  cap = want;
+  return 0;
+}
 
 namespace {
 struct CachedRes {
@@ -187,61 +172,6 @@ struct OtlpEngine {
   std::string err;
   ~OtlpEngine() { if (keys_dev) (void)hipFree(keys_dev); }
 };
-
-struct OtlpBatchImpl {
-  Engine* e = nullptr;
-  ose_columns cols{};
-  DevBuf arena, slab, stage, fixdev;   // device arena; device columns; pinned staging; host-pass records
-  std::vector<std::vector<std::pair<std::string, std::string>>> attrsets;
-  uint32_t host_spans = 0;
-  // which path the decode took (ose_otlp_walk_info): [0] the GPU chain linked,
-  // [1] resource-table misses, [2] of them entered into the table's key space
-  // (one Resource field or none), [3] scopes the host sized, [4] the scope
-  // redo, [5] the resource redo, [6] the span kernel (1 LDS-staged, 2 HBM),
-  // [7] the arena regrown
-  uint32_t walk_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  double t_ms[5] = {0, 0, 0, 0, 0};   // copy-in, walk, columns upload, span kernel (+ sync), host pass
-  // for ose_otlp_encode: the caller's message and where its parts are
-  const uint8_t* pb = nullptr;
-  size_t pb_len = 0;
-  std::vector<uint64_t> span_ref;
-  OtlpLayout lay;
-  // with the scopes walked on the GPU, span_ref and the scopes' span0 / hdr
-  // / schema are on the device until ose_otlp_encode (or the host pass)
-  // brings them back
-  bool layout_on_host = true;
-  DevBuf sslab;   // scope-level device arrays
-  DevBuf rslab, setbuf, cslab;   // resource-level device arrays; attribute-set compaction; the GPU chain walk
-  uint64_t* d_res_ref = nullptr;   // the ResourceSpans refs (lay.res_ref is filled from it on demand)
-  bool res_on_device = false;   // res_scope0 / scope_ref / attr_res live on the device (rslab, sslab)
-  uint32_t* d_res_scope0 = nullptr;
-  uint64_t* d_scope_ref = nullptr;
-  uint64_t* d_attr_res = nullptr;
-  uint64_t* d_span_ref = nullptr;
-  uint32_t *d_span_res = nullptr, *d_span0 = nullptr;
-  uint64_t *d_hdr = nullptr, *d_schema = nullptr;
-  OtlpScopeArgs sargs{};   // the GPU scope walk's arrays (pass 2 reuses them)
-  // the GPU encoder (encode_kernel.hip): the span refs in HBM (always), the
-  // scope level there when the GPU walked it; its workspace and outputs
-  uint64_t* d_spans = nullptr;
-  bool scopes_dev = false;
-  DevBuf eslab, eout, emisc;
-  DevBuf seth;   // pinned: the resource pass's attribute-set scan words and ids (read after the scope pass's wait)
-  // a batch released by a groupbytrace store (ose_gbt_release_otlp): the
-  // store owns it, `arena` is the released message buffer and every layout
-  // array is the store's; relhost takes the buffer when the host encoder runs
-  bool released = false;
-  DevBuf relhost;
-  // engine option otlp_condattr (on at the decode: ca_on): the stage's columns
-  // (ose_otlp_condattr_columns) for the engine's ca_keys keys, in a slab of
-  // their own; cafix takes the host pass's entries
-  bool ca_on = false;
-  uint32_t ca_keys = 0;
-  ose_condattr_columns ca{};
-  DevBuf caslab, cafix;
-  OtlpBatchImpl() { stage.host = true; emisc.host = true; seth.host = true; relhost.host = true; }
-};
-
 
 namespace {
 std::mutex g_otlp_mu;
@@ -756,6 +686,28 @@ bool walk(const ColumnizeCtx& ctx, ResCache& cache, const uint8_t* p, size_t n, 
 }
 }  // namespace
 
+// the walk and the spans' sizes for the encoder's CPU test seams (otlp_batch.hpp)
+int otlp_host_walk_sizes(const uint8_t* pb, size_t len, std::vector<uint64_t>& span_ref, OtlpLayout& lay,
+                         std::vector<uint32_t>& span_size) {
+  ColumnizeCtx ctx;
+  std::string err = ctx.build(nullptr, nullptr, nullptr);
+  Walked w;
+  ResCache cache;
+  if (err.empty() && !walk(ctx, cache, pb, len, w)) err = w.err;
+  if (!err.empty()) return fail(OSE_EINVAL, err);
+  span_size.resize(w.span_ref.size());
+  ProtoSizer sizer;
+  for (size_t i = 0; i < span_size.size(); i++) {
+    Span sp;
+    if (!pb_span(pb + (uint32_t)w.span_ref[i], (size_t)(w.span_ref[i] >> 32), sp))
+      return fail(OSE_EINVAL, "OTLP protobuf: malformed Span");
+    span_size[i] = (uint32_t)sizer.span(sp);
+  }
+  span_ref = std::move(w.span_ref);
+  lay = std::move(w.lay);
+  return 0;
+}
+
 namespace {
 // The GPU half of the structural walk: every ScopeSpans the host did not
 // walk is counted, sized and listed on the device (otlp_scope_*_kernel);
@@ -1197,6 +1149,7 @@ int scope_walk_gpu(Engine* e, OtlpBatchImpl* b, Walked& w, hipStream_t st, uint6
   b->layout_on_host = false;
   return 0;
 }
+}  // namespace
 
 // span refs and the scopes' span0 / header / schema refs back to the host
 // (the encoder and the host pass read them there)
@@ -1230,6 +1183,7 @@ int layout_to_host(OtlpBatchImpl* b, hipStream_t st) {
   return 0;
 }
 
+namespace {
 // ---- engine option otlp_condattr: odigosconditionalattributes' columns ----------
 // The span columns on the GPU: the batch's slab of them, span_has zeroed,
 // otlp_condattr_kernel behind the span kernel (before the host-pass count is
@@ -1891,220 +1845,6 @@ int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchIm
 }
 }  // namespace
 
-// ---- the GPU encoder (encode_kernel.hip) -------------------------------------------
-namespace {
-// 0 with *host false: *o holds the outputs; 0 with *host true: the host
-// encoder takes the call (o->fallback says why); else an error code
-// ca (ose_otlp_encode_condattr; sampled, tmpl and sql false): odigosconditionalattributes'
-// puts are applied, by the kernels' instances for them.
-int encode_gpu(OtlpBatchImpl* b, const ose_outputs* outs, bool sampled, bool tmpl, bool sql, const Router* router,
-               hipStream_t st, OtlpOut* o, bool* host, std::vector<uint64_t>* res_off = nullptr,
-               const ose_condattr_outputs* ca = nullptr) {
-  *host = true;
-  if (b->e->option(Engine::kOptEncodeHost)) return 0;   // engine option encode_host: the host encoder always
-  if (router && router->pipelines.size() > 63) return 0;   // the host encoder reports it
-  const uint32_t ca_T = ca ? (uint32_t)b->e->condattr_tab.target_key.size() : 0;
-  if (ca_T > kEncCaTargets) {   // the host encoder has no bound on the targets
-    o->fallback = kEncFbCa;
-    return 0;
-  }
-  const uint64_t n = b->cols.n_spans, S = b->cols.n_scopes, R = b->cols.n_resources;
-  if (!b->d_spans) return 0;
-  const uint32_t n_out = router ? (uint32_t)router->pipelines.size() + 1 : 1;
-  const uint32_t tiles = (uint32_t)std::max<uint64_t>(1, (R + kEncTiles - 1) / kEncTiles);
-  // workspace
-  EncArgs a{};
-  const size_t blob = router ? router->dev_blob.size() : 0;
-  struct Part { void** dst; size_t bytes; };
-  uint64_t* flags64 = nullptr;
-  uint32_t *scope_span0 = nullptr, *res_scope0 = nullptr;
-  uint64_t *scope_hdr = nullptr, *scope_schema = nullptr, *res_ref = nullptr;
-  uint8_t* routes = nullptr;
-  uint64_t* out_base = nullptr;
-  std::vector<Part> parts = {
-      {(void**)&a.span_out, 4 * n},
-      {(void**)&a.scope_body, 8 * S},
-      {(void**)&a.res_body, 8 * R},
-      {(void**)&a.res_rec, 8 * R},
-      {(void**)&a.res_mask, 8 * R},
-      {(void**)&a.res_hdr, 8 * R},
-      {(void**)&a.res_schema, 8 * R},
-      {(void**)&flags64, 8},
-      {(void**)&a.tile_sum, 16 * (size_t)n_out * tiles},
-      {(void**)&a.off, 8 * (size_t)n_out * R},
-      {(void**)&a.out_total, 16 * (size_t)n_out},
-      {(void**)&out_base, 8 * (size_t)n_out},
-  };
-  if (tmpl || sql) parts.push_back({(void**)&a.edit, sizeof(EncEdit) * n});
-  if (sql) parts.push_back({(void**)&a.sql_edit, sizeof(EncSqlEdit) * n});
-  EncCaArgs ca_a{};
-  if (ca) {   // the puts in the workspace (src / val may be host memory), and the new span lengths
-    parts.push_back({(void**)&ca_a.ca_src, (size_t)ca_T * n});
-    parts.push_back({(void**)&ca_a.ca_val, 8 * (size_t)ca_T * n});
-    parts.push_back({(void**)&ca_a.ca_len, 4 * n});
-  }
-  if (blob) parts.push_back({(void**)&routes, blob});
-  // the layout arrays the decoder left on the host go up
-  const bool up_scopes = !b->scopes_dev, up_res = !b->res_on_device;
-  if (up_scopes) {
-    parts.push_back({(void**)&scope_span0, 4 * S});
-    parts.push_back({(void**)&scope_hdr, 8 * S});
-    parts.push_back({(void**)&scope_schema, 8 * S});
-  }
-  if (up_res) {
-    parts.push_back({(void**)&res_ref, 8 * R});
-    parts.push_back({(void**)&res_scope0, 4 * R});
-  }
-  size_t total = 0;
-  for (auto& p : parts) total = up(total + p.bytes + 16);
-  int rc;
-  if ((rc = b->eslab.need(total))) return rc;
-  size_t off = 0;
-  for (auto& p : parts) {
-    *p.dst = b->eslab.p + off;
-    off = up(off + p.bytes + 16);
-  }
-  // host-side uploads through pinned staging: route table, layout, offsets
-  size_t hbytes = 64 + 16 * (size_t)n_out + 8 * (size_t)n_out + 16 + blob + 16;
-  if (up_scopes) hbytes += 20 * S + 64;
-  if (up_res) hbytes += 12 * R + 64;
-  if ((rc = b->emisc.need(hbytes))) return rc;
-  uint8_t* h = b->emisc.p;
-  size_t ho = up(64 + 16 * (size_t)n_out, 16);   // [0, 64): flags; then the totals
-  auto upload = [&](void* dst, const void* src, size_t bytes) -> int {
-    if (!bytes) return 0;
-    std::memcpy(h + ho, src, bytes);
-    HIP_TRY(hipMemcpyAsync(dst, h + ho, bytes, hipMemcpyHostToDevice, st));
-    ho = up(ho + bytes, 16);
-    return 0;
-  };
-  if (up_scopes && (b->lay.scope_span0.size() != S || b->lay.scope_hdr.size() != S || b->lay.scope_schema.size() != S))
-    return 0;
-  if (up_res && (b->lay.res_ref.size() != R || b->lay.res_scope0.size() != R)) return 0;
-  if (blob && (rc = upload(routes, router->dev_blob.data(), blob))) return rc;
-  if (up_scopes) {
-    std::vector<uint32_t> s0(b->lay.scope_span0.begin(), b->lay.scope_span0.end());
-    if ((rc = upload(scope_span0, s0.data(), 4 * S)) || (rc = upload(scope_hdr, b->lay.scope_hdr.data(), 8 * S)) ||
-        (rc = upload(scope_schema, b->lay.scope_schema.data(), 8 * S)))
-      return rc;
-  }
-  if (up_res &&
-      ((rc = upload(res_ref, b->lay.res_ref.data(), 8 * R)) || (rc = upload(res_scope0, b->lay.res_scope0.data(), 4 * R))))
-    return rc;
-  a.pb = b->arena.p;
-  a.n_spans = n;
-  a.n_scopes = S;
-  a.n_res = R;
-  a.span_ref = b->d_spans;
-  a.span_size = b->cols.span_size;
-  a.keep = sampled ? outs->keep : nullptr;
-  if (tmpl) {
-    a.url_out = outs->url_out;
-    a.tmpl = outs->tmpl;
-    a.tmpl_arena = outs->tmpl_arena;
-    a.tmpl_used = outs->tmpl_arena_used;
-  }
-  if (sql) a.sql_op = outs->sql_op;
-  a.scope_span0 = up_scopes ? scope_span0 : b->d_span0;
-  a.scope_hdr = up_scopes ? scope_hdr : b->d_hdr;
-  a.scope_schema = up_scopes ? scope_schema : b->d_schema;
-  a.scope_size = b->cols.scope_size;
-  a.res_ref = up_res ? res_ref : b->d_res_ref;
-  a.res_scope0 = up_res ? res_scope0 : b->d_res_scope0;
-  a.res_size = b->cols.res_size;
-  a.n_out = n_out;
-  a.route_bits = router ? router->route_bits : 0;
-  a.routes = reinterpret_cast<const EncRouteSlot*>(routes);
-  a.route_keys = routes ? routes + router->dev_slots_bytes : nullptr;
-  a.flags = reinterpret_cast<uint32_t*>(flags64);
-  a.out_base = out_base;
-  if ((n && !a.span_size) || (S && (!a.scope_span0 || !a.scope_hdr || !a.scope_schema || !a.scope_size)) ||
-      (R && (!a.res_ref || !a.res_scope0 || !a.res_size)))
-    return 0;
-  using clk = std::chrono::steady_clock;
-  auto t0 = clk::now();
-  // sizing pass, offsets
-  HIP_TRY(hipMemsetAsync(flags64, 0, 8, st));
-  if (ca) {
-    if ((uint64_t)ca_T * n) {
-      HIP_TRY(hipMemcpyAsync(const_cast<uint8_t*>(ca_a.ca_src), ca->src, (size_t)ca_T * n, hipMemcpyDefault, st));
-      HIP_TRY(hipMemcpyAsync(const_cast<ose_strref*>(ca_a.ca_val), ca->val, 8 * (size_t)ca_T * n, hipMemcpyDefault, st));
-    }
-    static_cast<EncArgs&>(ca_a) = a;
-    ca_a.ca_blob = b->e->condattr_blob_dev;
-    ca_a.ca_targets = ca_T;
-    ca_a.ca_string_bytes = b->e->condattr_tab.string_bytes;
-    ca_a.ca_arena_bytes = b->cols.arena_bytes;
-    launch_enc_spans_ca(ca_a, st);
-  } else {
-    launch_enc_spans(a, st);
-  }
-  HIP_TRY(hipGetLastError());
-  launch_enc_scopes(a, st);
-  HIP_TRY(hipGetLastError());
-  launch_enc_resources(a, st);
-  HIP_TRY(hipGetLastError());
-  launch_enc_scan(a, st);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(h, flags64, 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(h + 64, a.out_total, 16 * (size_t)n_out, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  uint32_t fb;
-  std::memcpy(&fb, h, 4);
-  o->fallback = fb;
-  o->t_ms[1] = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
-  t0 = clk::now();
-  if (fb) return 0;
-  std::vector<uint64_t> tot(2 * (size_t)n_out);
-  std::memcpy(tot.data(), h + 64, 16 * (size_t)n_out);
-  std::vector<uint64_t> base(n_out);
-  uint64_t all = 0;
-  for (uint32_t k = 0; k < n_out; k++) {
-    base[k] = all;
-    all = up(all + tot[k], 16);
-  }
-  if ((rc = b->eout.need(all + 16))) return rc;
-  a.out = b->eout.p;
-  if ((rc = upload(out_base, base.data(), 8 * (size_t)n_out))) return rc;
-  // host buffers (pinned, pooled with the workspace)
-  o->outs.assign(n_out, EncodedOutput{});
-  bool oom = false;
-  for (uint32_t k = 0; k < n_out; k++) {
-    EncodedOutput& x = o->outs[k];
-    x.name = router ? (k + 1 < n_out ? router->pipelines[k] : std::string("default")) : std::string();
-    x.len = tot[k];
-    x.n_resources = (uint32_t)tot[n_out + k];
-    x.data = encode_work_pinned(*o->work, x.len, &x.cap);
-    x.pinned = true;
-    oom |= x.data == nullptr;
-  }
-  if (oom) return fail(OSE_EDEVICE, "out of pinned host memory for the encoder outputs");
-  o->t_ms[2] = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
-  t0 = clk::now();
-  if (ca) {
-    static_cast<EncArgs&>(ca_a) = a;   // (a.out is set by now)
-    launch_enc_write_ca(ca_a, st);
-  } else {
-    launch_enc_write(a, st);
-  }
-  HIP_TRY(hipGetLastError());
-  for (uint32_t k = 0; k < n_out; k++)
-    if (tot[k]) HIP_TRY(hipMemcpyAsync(o->outs[k].data, a.out + base[k], tot[k], hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(h, flags64, 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  std::memcpy(&fb, h, 4);
-  if (fb & kEncFbWrite) return fail(OSE_EDEVICE, "GPU encoder: a record's bytes disagree with its size");
-  if (res_off) {   // each output's offset of every resource's record (the scan the writer used)
-    res_off->resize((size_t)n_out * R);
-    if (R) HIP_TRY(hipMemcpy(res_off->data(), a.off, 8 * (size_t)n_out * R, hipMemcpyDeviceToHost));
-  }
-  o->t_ms[3] = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
-  o->gpu = 1;
-  *host = false;
-  return 0;
-}
-}  // namespace
-
 // ---- batches of the groupbytrace store (gbt_host.cpp) ---------------------------
 void otlp_batch_view(const ose_otlp_batch* bb, OtlpBatchView* v) {
   const auto* b = reinterpret_cast<const OtlpBatchImpl*>(bb);
@@ -2155,41 +1895,6 @@ void otlp_released_set(ose_otlp_batch* bb, const ose_columns& cols, const OtlpRe
   b->d_res_ref = const_cast<uint64_t*>(l.res_ref);
   b->d_res_scope0 = const_cast<uint32_t*>(l.res_scope0);
   b->d_scope_ref = const_cast<uint64_t*>(l.scope_ref);
-}
-
-// The GPU encoder for the OTLP pipeline (otlp_pipeline.cpp): *out holds the
-// batch's outputs and res_off every output's per-resource record offsets
-// (n_out x R); *gpu false when the GPU encoder declined the batch (nothing
-// in *out), the caller then takes its requests one by one.
-int otlp_encode_gpu_offsets(Engine* e, ose_otlp_batch* bb, const ose_outputs* outs, uint32_t stages,
-                            const Router* router, hipStream_t st, OtlpOut** out, std::vector<uint64_t>& res_off,
-                            bool* gpu) {
-  auto* b = reinterpret_cast<OtlpBatchImpl*>(bb);
-  *gpu = false;
-  *out = nullptr;
-  auto* o = new OtlpOut();
-  o->e = e;
-  engine_retain(e);
-  {
-    std::lock_guard<std::mutex> g(e->mu);
-    if (!e->enc_pool.empty()) {
-      o->work = static_cast<EncodeWork*>(e->enc_pool.back());
-      e->enc_pool.pop_back();
-    }
-  }
-  if (!o->work) o->work = encode_work_new();
-  const bool sampled = stages & (OSE_STAGE_SAMPLE | OSE_STAGE_APPLY_KEEP);
-  const bool tmpl = stages & OSE_STAGE_TEMPLATE;
-  const bool sql = stages & (OSE_STAGE_SQLOP | OSE_STAGE_APPLY_SQLOP);
-  bool host = true;
-  const int rc = encode_gpu(b, outs, sampled, tmpl, sql, router, st, o, &host, &res_off);
-  if (rc || host) {
-    otlp_out_release(o);
-    return rc;
-  }
-  *gpu = true;
-  *out = o;
-  return 0;
 }
 
 }  // namespace ose
@@ -2356,137 +2061,6 @@ int ose_otlp_attrset(const ose_otlp_batch* bb, uint32_t k, char* json, size_t ca
   return 0;
 }
 
-namespace {
-int encode_threads() { return parallel_width(); }
-}  // namespace
-
-int ose_otlp_encode(ose_engine* eng, const ose_otlp_batch* bb, const ose_outputs* outs, uint32_t stages,
-                    uint32_t group_mode, const ose_router* router, void* hip_stream, ose_otlp_out** out) {
-  if (!eng || !bb || !out) return fail(OSE_EINVAL, "NULL argument");
-  if (stages & OSE_STAGE_CONDATTR) return refuse_condattr("ose_otlp_encode");
-  Engine* e = reinterpret_cast<Engine*>(eng);
-  // odigossqldboperationprocessor's attribute and name are written only under
-  // the engine option otlp_sqlop (the default until the next ABI version: refused)
-  const bool sql = (stages & (OSE_STAGE_SQLOP | OSE_STAGE_APPLY_SQLOP)) != 0;
-  if (sql && !(e->has_sqlop && e->option(Engine::kOptOtlpSqlop)))
-    return fail(OSE_ENOTSUP, "ose_otlp_encode does not write odigossqldboperationprocessor's attribute and span name "
-                             "(engine option otlp_sqlop is off)");
-  if ((stages & OSE_STAGE_SQLOP) && (stages & OSE_STAGE_APPLY_SQLOP))
-    return fail(OSE_EINVAL, "OSE_STAGE_APPLY_SQLOP and OSE_STAGE_SQLOP exclude each other");
-  if (sql && (!outs || !outs->sql_op)) return fail(OSE_EINVAL, "sql_op is NULL");
-  auto* b = const_cast<OtlpBatchImpl*>(reinterpret_cast<const OtlpBatchImpl*>(bb));
-  if (b->e != e) return fail(OSE_EINVAL, "the batch belongs to another engine");
-  if (int rc = bind_device(e)) return rc;
-  const bool batch_mode = (stages & OSE_STAGE_SAMPLE) && group_mode == OSE_GROUP_BATCH;
-  const bool sampled = (stages & (OSE_STAGE_SAMPLE | OSE_STAGE_APPLY_KEEP)) && !batch_mode;
-  const bool tmpl = stages & OSE_STAGE_TEMPLATE;
-  if ((sampled || batch_mode || tmpl) && !outs) return fail(OSE_EINVAL, "NULL outputs");
-  if (sampled && !outs->keep) return fail(OSE_EINVAL, "keep is NULL");
-  if (batch_mode && !outs->trace_keep) return fail(OSE_EINVAL, "trace_keep is NULL");
-  if (tmpl && (!outs->url_out || !outs->tmpl || !outs->tmpl_arena || !outs->tmpl_arena_used))
-    return fail(OSE_EINVAL, "template outputs are NULL");
-  hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  const auto t_start = std::chrono::steady_clock::now();
-  const uint64_t n = b->cols.n_spans;
-  uint32_t gpu_fallback = 0;
-  if (!batch_mode) {   // the GPU encoder (OSE_GROUP_BATCH's all-or-nothing stays with the host)
-    auto* o = new OtlpOut();
-    o->e = e;
-    engine_retain(e);   // dropped by otlp_out_release
-    {
-      std::lock_guard<std::mutex> g(e->mu);
-      if (!e->enc_pool.empty()) {
-        o->work = static_cast<EncodeWork*>(e->enc_pool.back());
-        e->enc_pool.pop_back();
-      }
-    }
-    if (!o->work) o->work = encode_work_new();
-    bool host = true;
-    const int rc = encode_gpu(b, outs, sampled, tmpl, sql, reinterpret_cast<const Router*>(router), st, o, &host);
-    if (rc || host) {
-      gpu_fallback = o->fallback;
-      otlp_out_release(o);   // pinned buffers taken before a failure go back to the work's pool
-      if (rc) return rc;
-    } else {
-      *out = reinterpret_cast<ose_otlp_out*>(o);
-      return 0;
-    }
-  }
-  // the decisions and the decoder's span sizes, D2H into the batch's pinned staging
-  const size_t o_keep = 0, o_url = up(n + 16), o_tmpl = o_url + up(n + 16), o_size = o_tmpl + up(8 * n + 16),
-               o_misc = o_size + up(4 * n + 16), o_sql = o_misc + 256, o_arena = o_sql + up(n + 16);
-  int rc;
-  if ((rc = b->stage.need(o_arena))) return rc;
-  uint8_t* h = b->stage.p;
-  if (n) HIP_TRY(hipMemcpyAsync(h + o_size, b->cols.span_size, 4 * n, hipMemcpyDeviceToHost, st));
-  if (sampled && n) HIP_TRY(hipMemcpyAsync(h + o_keep, outs->keep, n, hipMemcpyDefault, st));
-  if (batch_mode) HIP_TRY(hipMemcpyAsync(h + o_misc + 8, outs->trace_keep, 1, hipMemcpyDefault, st));
-  if (sql && n) HIP_TRY(hipMemcpyAsync(h + o_sql, outs->sql_op, n, hipMemcpyDefault, st));
-  if (tmpl) {
-    if (n) HIP_TRY(hipMemcpyAsync(h + o_url, outs->url_out, n, hipMemcpyDefault, st));
-    if (n) HIP_TRY(hipMemcpyAsync(h + o_tmpl, outs->tmpl, 8 * n, hipMemcpyDefault, st));
-    HIP_TRY(hipMemcpyAsync(h + o_misc, outs->tmpl_arena_used, 8, hipMemcpyDefault, st));
-  }
-  HIP_TRY(hipStreamSynchronize(st));
-  uint64_t used = 0;
-  if (tmpl) {
-    std::memcpy(&used, h + o_misc, 8);
-    if (used > outs->tmpl_arena_cap) return fail(OSE_ERANGE, "tmpl_arena_used beyond tmpl_arena_cap");
-    if (used) {
-      if ((rc = b->stage.need(o_arena + used))) return rc;   // grow-only: earlier contents are lost
-      h = b->stage.p;
-      if (n) HIP_TRY(hipMemcpyAsync(h + o_size, b->cols.span_size, 4 * n, hipMemcpyDeviceToHost, st));
-      if (sampled && n) HIP_TRY(hipMemcpyAsync(h + o_keep, outs->keep, n, hipMemcpyDefault, st));
-      if (n) HIP_TRY(hipMemcpyAsync(h + o_url, outs->url_out, n, hipMemcpyDefault, st));
-      if (n) HIP_TRY(hipMemcpyAsync(h + o_tmpl, outs->tmpl, 8 * n, hipMemcpyDefault, st));
-      if (batch_mode) HIP_TRY(hipMemcpyAsync(h + o_misc + 8, outs->trace_keep, 1, hipMemcpyDefault, st));
-      if (sql && n) HIP_TRY(hipMemcpyAsync(h + o_sql, outs->sql_op, n, hipMemcpyDefault, st));
-      HIP_TRY(hipMemcpyAsync(h + o_arena, outs->tmpl_arena, used, hipMemcpyDefault, st));
-      HIP_TRY(hipStreamSynchronize(st));
-    }
-  }
-  EncodeDecisions d;
-  d.keep = sampled ? h + o_keep : nullptr;
-  d.drop_all = batch_mode && !h[o_misc + 8];
-  if (tmpl) {
-    d.url_out = h + o_url;
-    d.tmpl = reinterpret_cast<const ose_strref*>(h + o_tmpl);
-    d.tmpl_arena = h + o_arena;
-    d.tmpl_arena_len = used;
-  }
-  d.span_size = reinterpret_cast<const uint32_t*>(h + o_size);
-  if (sql) d.sql_op = h + o_sql;
-  if (b->released && !b->layout_on_host) {   // the released message buffer comes down once per release
-    const size_t len = b->cols.arena_bytes;
-    if ((rc = b->relhost.need(len + 16))) return rc;
-    if (len) HIP_TRY(hipMemcpyAsync(b->relhost.p, b->arena.p, len, hipMemcpyDeviceToHost, st));
-    b->pb = b->relhost.p;
-    b->pb_len = len;
-  }
-  if ((rc = layout_to_host(b, st))) return rc;
-  auto* o = new OtlpOut();
-  o->e = e;
-  engine_retain(e);   // dropped by otlp_out_release
-  {
-    std::lock_guard<std::mutex> g(e->mu);
-    if (!e->enc_pool.empty()) {
-      o->work = static_cast<EncodeWork*>(e->enc_pool.back());
-      e->enc_pool.pop_back();
-    }
-  }
-  if (!o->work) o->work = encode_work_new();
-  o->fallback = gpu_fallback;
-  o->t_ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
-  std::string err;
-  if (!encode_traces(b->pb, b->pb_len, b->span_ref, b->lay, d, reinterpret_cast<const Router*>(router),
-                     encode_threads(), *o->work, o->outs, err, o->t_ms + 1)) {
-    otlp_out_release(o);
-    return fail(OSE_EINVAL, err);
-  }
-  *out = reinterpret_cast<ose_otlp_out*>(o);
-  return 0;
-}
-
 const ose_condattr_columns* ose_otlp_condattr_columns(const ose_otlp_batch* bb) {
   if (!bb) return nullptr;
   const auto* b = reinterpret_cast<const OtlpBatchImpl*>(bb);
@@ -2511,204 +2085,6 @@ int ose_otlp_condattr_download(const ose_otlp_batch* bb, const ose_condattr_colu
   };
   for (auto& f : fs)
     if (f.src && f.dst && f.bytes) HIP_TRY(hipMemcpy(const_cast<void*>(f.dst), f.src, f.bytes, hipMemcpyDefault));
-  return 0;
-}
-
-int ose_otlp_encode_condattr(ose_engine* eng, const ose_otlp_batch* bb, const ose_condattr_outputs* ca,
-                             const ose_router* router, void* hip_stream, ose_otlp_out** out) {
-  if (!eng || !bb || !out) return fail(OSE_EINVAL, "NULL argument");
-  Engine* e = reinterpret_cast<Engine*>(eng);
-  if (!(e->has_condattr && e->option(Engine::kOptOtlpCondattr)))
-    return fail(OSE_ENOTSUP, "ose_otlp_encode_condattr: the engine option otlp_condattr is off");
-  auto* b = const_cast<OtlpBatchImpl*>(reinterpret_cast<const OtlpBatchImpl*>(bb));
-  if (b->released) return fail(OSE_EINVAL, "ose_otlp_encode_condattr does not take a batch released by a groupbytrace store");
-  if (b->e != e) return fail(OSE_EINVAL, "the batch belongs to another engine");
-  if (!b->ca_on) return fail(OSE_EINVAL, "the batch was decoded with the engine option otlp_condattr off");
-  const CondAttrCompiled& tab = e->condattr_tab;
-  const uint64_t n = b->cols.n_spans;
-  const uint32_t T = (uint32_t)tab.target_key.size();
-  if (!ca || ((uint64_t)T * n && (!ca->src || !ca->val))) return fail(OSE_EINVAL, "src or val is NULL");
-  if (int rc = bind_device(e)) return rc;
-  hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  const auto t_start = std::chrono::steady_clock::now();
-  uint32_t gpu_fallback = 0;
-  {   // the GPU encoder
-    auto* o = new OtlpOut();
-    o->e = e;
-    engine_retain(e);   // dropped by otlp_out_release
-    {
-      std::lock_guard<std::mutex> g(e->mu);
-      if (!e->enc_pool.empty()) {
-        o->work = static_cast<EncodeWork*>(e->enc_pool.back());
-        e->enc_pool.pop_back();
-      }
-    }
-    if (!o->work) o->work = encode_work_new();
-    bool host = true;
-    const int rc = encode_gpu(b, nullptr, false, false, false, reinterpret_cast<const Router*>(router), st, o, &host, nullptr, ca);
-    if (rc || host) {
-      gpu_fallback = o->fallback;
-      otlp_out_release(o);
-      if (rc) return rc;
-    } else {
-      *out = reinterpret_cast<ose_otlp_out*>(o);
-      return 0;
-    }
-  }
-  // the host encoder: the puts, the decoder's span sizes and what the decode
-  // put behind the message bytes, D2H into the batch's pinned staging
-  const uint64_t tail_base = std::min<uint64_t>(b->pb_len, b->cols.arena_bytes), tail = b->cols.arena_bytes - tail_base;
-  const size_t o_src = 0, o_val = up((size_t)T * n + 16), o_size = o_val + up(8 * (size_t)T * n + 16),
-               o_tail = o_size + up(4 * n + 16), o_end = o_tail + up(tail + 16);
-  int rc;
-  if ((rc = b->stage.need(o_end))) return rc;
-  uint8_t* h = b->stage.p;
-  if ((uint64_t)T * n) {
-    HIP_TRY(hipMemcpyAsync(h + o_src, ca->src, (size_t)T * n, hipMemcpyDefault, st));
-    HIP_TRY(hipMemcpyAsync(h + o_val, ca->val, 8 * (size_t)T * n, hipMemcpyDefault, st));
-  }
-  if (n) HIP_TRY(hipMemcpyAsync(h + o_size, b->cols.span_size, 4 * n, hipMemcpyDeviceToHost, st));
-  if (tail) HIP_TRY(hipMemcpyAsync(h + o_tail, b->arena.p + tail_base, tail, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  std::string err;
-  if ((rc = condattr_check_puts(h + o_src, reinterpret_cast<const ose_strref*>(h + o_val), n, T, b->cols.arena_bytes,
-                                tab.string_bytes, err)))
-    return fail(rc, err);
-  std::vector<std::string> names(T);
-  for (uint32_t u = 0; u < T; u++) names[u] = tab.keys[tab.target_key[u]];
-  EncodeDecisions d;
-  d.span_size = reinterpret_cast<const uint32_t*>(h + o_size);
-  if ((uint64_t)T * n) {
-    d.ca_src = h + o_src;
-    d.ca_val = reinterpret_cast<const ose_strref*>(h + o_val);
-    d.ca_targets = T;
-    d.ca_names = names.data();
-    d.ca_arena = b->pb;
-    d.ca_tail_base = tail_base;
-    d.ca_tail = h + o_tail;
-    d.ca_strings = tab.blob.data() + tab.strings_off;
-  }
-  if ((rc = layout_to_host(b, st))) return rc;
-  auto* o = new OtlpOut();
-  o->e = e;
-  engine_retain(e);   // dropped by otlp_out_release
-  {
-    std::lock_guard<std::mutex> g(e->mu);
-    if (!e->enc_pool.empty()) {
-      o->work = static_cast<EncodeWork*>(e->enc_pool.back());
-      e->enc_pool.pop_back();
-    }
-  }
-  if (!o->work) o->work = encode_work_new();
-  o->fallback = gpu_fallback;
-  o->t_ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
-  if (!encode_traces(b->pb, b->pb_len, b->span_ref, b->lay, d, reinterpret_cast<const Router*>(router), encode_threads(),
-                     *o->work, o->outs, err, o->t_ms + 1)) {
-    otlp_out_release(o);
-    return fail(OSE_EINVAL, err);
-  }
-  *out = reinterpret_cast<ose_otlp_out*>(o);
-  return 0;
-}
-
-// Test seam (CPU): the encoder on the host walk of `pb` with the given
-// decisions (keep / url_out / tmpl NULL when absent) and span sizes
-// computed on the host as the decoder would.  sql_op: OSE_SQLOP_* per span
-// (odigossqldboperationprocessor's decisions), NULL when absent.
-int osehost_otlp_encode_sql(const uint8_t* pb, size_t len, const uint8_t* keep, int drop_all, const uint8_t* url_out,
-                            const ose_strref* tmpl, const uint8_t* tmpl_arena, uint64_t tmpl_arena_len,
-                            const ose_router* router, int threads, ose_otlp_out** out, const uint8_t* sql_op) {
-  if ((!pb && len) || !out) return fail(OSE_EINVAL, "NULL argument");
-  ColumnizeCtx ctx;
-  std::string err = ctx.build(nullptr, nullptr, nullptr);
-  Walked w;
-  ResCache cache;
-  if (err.empty() && !walk(ctx, cache, pb, len, w)) err = w.err;
-  if (!err.empty()) return fail(OSE_EINVAL, err);
-  std::vector<uint32_t> sizes(w.span_ref.size());
-  ProtoSizer sizer;
-  for (size_t i = 0; i < sizes.size(); i++) {
-    Span sp;
-    if (!pb_span(pb + (uint32_t)w.span_ref[i], (size_t)(w.span_ref[i] >> 32), sp))
-      return fail(OSE_EINVAL, "OTLP protobuf: malformed Span");
-    sizes[i] = (uint32_t)sizer.span(sp);
-  }
-  EncodeDecisions d;
-  d.keep = keep;
-  d.drop_all = drop_all != 0;
-  d.url_out = url_out;
-  d.tmpl = tmpl;
-  d.tmpl_arena = tmpl_arena;
-  d.tmpl_arena_len = tmpl_arena_len;
-  d.span_size = sizes.data();
-  d.sql_op = sql_op;
-  auto* o = new OtlpOut();
-  o->work = encode_work_new();
-  if (!encode_traces(pb, len, w.span_ref, w.lay, d, reinterpret_cast<const Router*>(router),
-                     threads > 0 ? threads : encode_threads(), *o->work, o->outs, err, o->t_ms + 1)) {
-    otlp_out_release(o);
-    return fail(OSE_EINVAL, err);
-  }
-  *out = reinterpret_cast<ose_otlp_out*>(o);
-  return 0;
-}
-
-int osehost_otlp_encode(const uint8_t* pb, size_t len, const uint8_t* keep, int drop_all, const uint8_t* url_out,
-                        const ose_strref* tmpl, const uint8_t* tmpl_arena, uint64_t tmpl_arena_len,
-                        const ose_router* router, int threads, ose_otlp_out** out) {
-  return osehost_otlp_encode_sql(pb, len, keep, drop_all, url_out, tmpl, tmpl_arena, tmpl_arena_len, router, threads, out,
-                                 nullptr);
-}
-
-// Test seam (CPU): the host encoder applying odigosconditionalattributes' puts
-// (what ose_otlp_encode_condattr's host path runs) on the host walk of `pb`.
-// src / val: [n_targets * n_spans] as ose_condattr_outputs, host memory;
-// arena: the bytes OSE_CA_ARENA values point into; strings: the string table
-// of OSE_CA_CONFIG values; names: the target names' bytes back to back, their
-// lengths in name_lens.  n_spans other than the message's is OSE_EINVAL; src
-// and val are checked as ose_otlp_encode_condattr checks them.
-int osehost_otlp_encode_condattr(const uint8_t* pb, size_t len, uint64_t n_spans, const uint8_t* src,
-                                 const ose_strref* val, uint32_t n_targets, const uint8_t* arena, uint64_t arena_bytes,
-                                 const uint8_t* strings, uint64_t string_bytes, const uint8_t* names,
-                                 const uint32_t* name_lens, const ose_router* router, int threads, ose_otlp_out** out) {
-  if ((!pb && len) || !out) return fail(OSE_EINVAL, "NULL argument");
-  if (n_targets && n_spans && (!src || !val)) return fail(OSE_EINVAL, "src or val is NULL");
-  if (n_targets && !name_lens) return fail(OSE_EINVAL, "NULL argument");
-  ColumnizeCtx ctx;
-  std::string err = ctx.build(nullptr, nullptr, nullptr);
-  Walked w;
-  ResCache cache;
-  if (err.empty() && !walk(ctx, cache, pb, len, w)) err = w.err;
-  if (!err.empty()) return fail(OSE_EINVAL, err);
-  if (w.span_ref.size() != n_spans) return fail(OSE_EINVAL, "n_spans is not the message's span count");
-  if (int rc = condattr_check_puts(src, val, n_spans, n_targets, arena_bytes, string_bytes, err)) return fail(rc, err);
-  std::vector<uint32_t> sizes(w.span_ref.size());
-  ProtoSizer sizer;
-  for (size_t i = 0; i < sizes.size(); i++) {
-    Span sp;
-    if (!pb_span(pb + (uint32_t)w.span_ref[i], (size_t)(w.span_ref[i] >> 32), sp))
-      return fail(OSE_EINVAL, "OTLP protobuf: malformed Span");
-    sizes[i] = (uint32_t)sizer.span(sp);
-  }
-  std::vector<std::string> target_names(n_targets);
-  for (uint32_t u = 0, at = 0; u < n_targets; at += name_lens[u], u++)
-    target_names[u].assign(reinterpret_cast<const char*>(names) + at, name_lens[u]);
-  EncodeDecisions d;
-  d.span_size = sizes.data();
-  d.ca_src = src;
-  d.ca_val = val;
-  d.ca_targets = n_targets;
-  d.ca_names = target_names.data();
-  d.ca_arena = arena;
-  d.ca_strings = strings;
-  auto* o = new OtlpOut();
-  o->work = encode_work_new();
-  if (!encode_traces(pb, len, w.span_ref, w.lay, d, reinterpret_cast<const Router*>(router),
-                     threads > 0 ? threads : encode_threads(), *o->work, o->outs, err, o->t_ms + 1)) {
-    otlp_out_release(o);
-    return fail(OSE_EINVAL, err);
-  }
-  *out = reinterpret_cast<ose_otlp_out*>(o);
   return 0;
 }
 

@@ -2,7 +2,7 @@
 // as one device batch per wave of calls (ose_otlp_pipeline_*).
 //
 // Each ConsumeTraces of the OTLP path (decode -> SAMPLE | TEMPLATE | SIZE ->
-// route + re-encode, otlp_host.cpp) pays a chain of launches, copies and host
+// route + re-encode; otlp_host.cpp, otlp_encode_host.cpp) pays a chain of launches, copies and host
 // waits that an 8192-span request cannot amortise: round 5 measured 0.92 ms
 // per call at one caller and 33 M spans/s at eight, no faster than the CPU
 // baseline.  The pipeline lets concurrent callers share that chain:

@@ -336,12 +336,6 @@ void release_exchange_scratch(const Engine* e) {
 
 using namespace ose;
 
-#define HIP_TRY(expr)                                                                                  \
-  do {                                                                                                 \
-    hipError_t _e = (expr);                                                                            \
-    if (_e != hipSuccess) return fail(OSE_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
 namespace ose {
 namespace {
 // The owner's decisions for n received records (keep per record, recv in

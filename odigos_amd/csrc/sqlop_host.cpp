@@ -7,12 +7,6 @@
 
 namespace ose {
 
-#define HIP_TRY(expr)                                                                                  \
-  do {                                                                                                 \
-    hipError_t _e = (expr);                                                                            \
-    if (_e != hipSuccess) return fail(OSE_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
 // DBOperationProcessor.processTraces (processor.go:30-78): one plain launch
 // on the caller's stream, every span classified whatever keep says (the
 // reference runs after odigossampling removed the dropped spans; their

@@ -1,4 +1,4 @@
-"""The OTLP encoder (encode_kernel.hip, encode_gpu in otlp_host.cpp, and the
+"""The OTLP encoder (encode_kernel.hip, encode_gpu in otlp_encode_host.cpp, and the
 host encoder otlp_encode.cpp) on hand-laid messages at every scan, wave and
 routing seam (tests/encode_layouts.py).
 

@@ -1,5 +1,6 @@
 """groupbytrace on the OTLP path: ose_gbt_add_otlp / ose_gbt_release_otlp
-(gbt_host.cpp, gbt_kernel.hip, otlp_host.cpp).
+(gbt_host.cpp, gbt_kernel.hip, the released batch in otlp_host.cpp, its
+encode in otlp_encode_host.cpp).
 
 decode -> add_otlp -> release_otlp -> stages -> encode, no pdata in between:
 an OTLP-fed store keeps every span's message and every added scope's header
