@@ -96,7 +96,7 @@ void columnize_condattr(const std::vector<std::string>& keys, size_t n_targets, 
 // of key-major columns: has, val = the value's AsString appended to `arena`
 // (a ref from arena_base on) and, when kv_size is not NULL, the KeyValue's
 // framed size in a span (field 9).  The one lookup of columnize_condattr and
-// of the OTLP decoder's host-made columns (otlp_host.cpp).
+// of the OTLP decoder's host-made columns (otlp_condattr_host.cpp).
 void condattr_lookup(const std::vector<std::string>& keys, const AttrMap& m, size_t row, size_t rows, std::string& arena,
                      size_t arena_base, const ProtoSizer& sizer, uint8_t* has, ose_strref* val, uint32_t* kv_size);
 

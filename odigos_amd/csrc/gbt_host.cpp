@@ -29,12 +29,11 @@
 
 #include "engine_internal.hpp"
 #include "kernels.hpp"
+#include "slab.hpp"
 
 namespace ose {
 
 namespace {
-size_t up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
-
 struct DevMem {   // grow-only device buffer
   uint8_t* p = nullptr;
   size_t cap = 0;
@@ -611,9 +610,8 @@ int gbt_release(Gbt* g, int64_t now, hipStream_t st, uint32_t* n_traces, bool ot
     if ((rc = sort_pairs(g, a.keys, a.vals, m, bits, st, &skeys, &order))) return rc;
     // the released batch: fixed columns and fragment heads, then strings and fragments
     const uint64_t M = std::max<uint64_t>(m, 1), K = g->K;
-    struct Part { void** dst; size_t bytes; };
     GbtOut& O = a.out;
-    std::vector<Part> parts = {
+    std::vector<SlabPart> parts = {
         {(void**)&O.tid, 16 * M}, {(void**)&O.start, 8 * M}, {(void**)&O.end, 8 * M},
         {(void**)&O.attr_match, 8 * M * g->e->attr_words}, {(void**)&O.status, M}, {(void**)&O.kind, M},
         {(void**)&O.url_flags, M}, {(void**)&O.span_size, 4 * M}, {(void**)&O.name_len, 4 * M},
@@ -623,24 +621,16 @@ int gbt_release(Gbt* g, int64_t now, hipStream_t st, uint32_t* n_traces, bool ot
         {(void**)&O.res_size, 4 * M}, {(void**)&O.scope_size, 4 * M}, {(void**)&O.scope_resource, 4 * M},
         {(void**)&O.res_url_ok, M},
     };
-    if (g->sql) {
-      parts.push_back({(void**)&O.db_flags, M});
-      parts.push_back({(void**)&O.db_query, 8 * M});
-      parts.push_back({(void**)&O.res_sql_ok, M});
-    }
+    if (g->sql) parts.insert(parts.end(), {{(void**)&O.db_flags, M}, {(void**)&O.db_query, 8 * M}, {(void**)&O.res_sql_ok, M}});
     if (otlp) {   // what the GPU encoder reads: per span, per fragment (at most m)
       GbtOtlp& X = a.otlp;
-      parts.push_back({(void**)&X.out_span_ref, 8 * M});
-      parts.push_back({(void**)&X.out_span0, 4 * M});
-      parts.push_back({(void**)&X.out_res_scope0, 4 * M});
-      parts.push_back({(void**)&X.out_hdr, 8 * M});
-      parts.push_back({(void**)&X.out_schema, 8 * M});
-      parts.push_back({(void**)&X.out_res_ref, 8 * M});
-      parts.push_back({(void**)&X.out_scope_ref, 8 * M});
+      parts.insert(parts.end(), {
+          {(void**)&X.out_span_ref, 8 * M}, {(void**)&X.out_span0, 4 * M}, {(void**)&X.out_res_scope0, 4 * M},
+          {(void**)&X.out_hdr, 8 * M}, {(void**)&X.out_schema, 8 * M}, {(void**)&X.out_res_ref, 8 * M},
+          {(void**)&X.out_scope_ref, 8 * M},
+      });
     }
-    size_t total = 0;
-    for (auto& p : parts) total = up(total + p.bytes + 16);
-    const size_t arena_at = total;
+    const size_t arena_at = slab_size(parts).total;
     // the strings of the released spans are at most the live arena bytes
     // (OTLP: a header block leaves once per released fragment, so the live
     // bytes are no bound; the message buffer is the released batch's own and
@@ -651,11 +641,7 @@ int gbt_release(Gbt* g, int64_t now, hipStream_t st, uint32_t* n_traces, bool ot
     // bytes after arena_bytes.  arena_at is a multiple of 256 in a 256-byte
     // aligned allocation, and 64 bytes follow the last string.
     if ((rc = g->out.need(arena_at + up(arena_bound + 64)))) return rc;
-    size_t off = 0;
-    for (auto& p : parts) {
-      *p.dst = g->out.p + off;
-      off = up(off + p.bytes + 16);
-    }
+    slab_assign(parts, g->out.p);
     O.arena = g->out.p + arena_at;
     a.n = m;
     a.order = order;
@@ -803,8 +789,7 @@ int ose_gbt_create(ose_engine* eng, const char* cfg_json, uint64_t span_capacity
   g->wcnt.assign(g->W, 0);
   g->wrel.assign(g->W, 0);
   const uint64_t C = g->pool_cap, K = g->K;
-  struct Part { void** dst; size_t bytes; };
-  std::vector<Part> parts = {
+  std::vector<SlabPart> parts = {
       {(void**)&g->P.tid, 16 * C}, {(void**)&g->P.start, 8 * C}, {(void**)&g->P.end, 8 * C},
       {(void**)&g->P.attr_match, 8 * C * g->e->attr_words}, {(void**)&g->P.seq, 8 * C}, {(void**)&g->P.origin, 8 * C},
       {(void**)&g->P.str_off, 8 * C}, {(void**)&g->P.status, C}, {(void**)&g->P.kind, C},
@@ -812,37 +797,22 @@ int ose_gbt_create(ose_engine* eng, const char* cfg_json, uint64_t span_capacity
       {(void**)&g->P.route, 8 * C}, {(void**)&g->P.path, 8 * C}, {(void**)&g->P.attr_type, K * C + 16},
       {(void**)&g->P.attr_val, 8 * K * C + 16},
   };
-  if (g->sql) {
-    parts.push_back({(void**)&g->P.db_flags, C});
-    parts.push_back({(void**)&g->P.db_query, 8 * C});
-  }
-  size_t total = 0;
-  for (auto& p : parts) total = up(total + p.bytes + 16);
+  if (g->sql) parts.insert(parts.end(), {{(void**)&g->P.db_flags, C}, {(void**)&g->P.db_query, 8 * C}});
   const uint64_t SC = g->scope_cap;
-  std::vector<Part> sparts = {
+  std::vector<SlabPart> sparts = {
       {(void**)&g->Q.res_svc, 4 * SC}, {(void**)&g->Q.res_svc_str, 4 * SC}, {(void**)&g->Q.res_attrset, 4 * SC},
       {(void**)&g->Q.res_size, 4 * SC}, {(void**)&g->Q.scope_size, 4 * SC}, {(void**)&g->Q.res_url_ok, SC},
   };
   if (g->sql) sparts.push_back({(void**)&g->Q.res_sql_ok, SC});
-  size_t stotal = 0;
-  for (auto& p : sparts) stotal = up(stotal + p.bytes + 16);
   int rc;
-  if ((rc = g->pool.need(total)) || (rc = g->scopes.need(stotal)) || (rc = g->arena.need(g->arena_cap)) ||
-      (rc = g->ring.need(16 * g->ring_n)) || (rc = g->words.need(1 << 16)) ||
+  if ((rc = g->pool.need(slab_size(parts).total)) || (rc = g->scopes.need(slab_size(sparts).total)) ||
+      (rc = g->arena.need(g->arena_cap)) || (rc = g->ring.need(16 * g->ring_n)) || (rc = g->words.need(1 << 16)) ||
       (g->W > 1 && ((rc = g->tinfo.need(8 * g->ring_n)) || (rc = g->wdev.need(up(8ull * g->W) + 2 * up(4ull * g->W + 16)))))) {
     delete g;
     return rc;
   }
-  size_t off = 0;
-  for (auto& p : parts) {
-    *p.dst = g->pool.p + off;
-    off = up(off + p.bytes + 16);
-  }
-  off = 0;
-  for (auto& p : sparts) {
-    *p.dst = g->scopes.p + off;
-    off = up(off + p.bytes + 16);
-  }
+  slab_assign(parts, g->pool.p);
+  slab_assign(sparts, g->scopes.p);
   engine_retain(e);   // dropped by ose_gbt_destroy
   *out = reinterpret_cast<ose_gbt*>(g);
   return 0;

@@ -1,6 +1,8 @@
-// otlp_batch.hpp — the decoded OTLP batch (ose_otlp_batch), as its two host
+// otlp_batch.hpp — the decoded OTLP batch (ose_otlp_batch), as its three host
 // files share it: otlp_host.cpp makes and owns it (decode, the accessors,
-// release), otlp_encode_host.cpp re-encodes from it.  Internal to those two.
+// release), otlp_condattr_host.cpp adds odigosconditionalattributes' columns
+// during the decode, otlp_encode_host.cpp re-encodes from it.  Internal to
+// those three.
 #pragma once
 #include <string>
 #include <utility>
@@ -9,10 +11,9 @@
 #include "engine_internal.hpp"
 #include "kernels.hpp"
 #include "otlp_encode.hpp"
+#include "slab.hpp"
 
 namespace ose {
-
-inline size_t up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
 struct DevBuf {   // grow-only device (or pinned host) buffer
   uint8_t* p = nullptr;
@@ -78,9 +79,29 @@ struct OtlpBatchImpl {
   OtlpBatchImpl() { stage.host = true; emisc.host = true; seth.host = true; relhost.host = true; }
 };
 
-// What the encoder needs of the decoder's file (otlp_host.cpp).
+// The host-pass list the span kernels (span, sqlop, condattr) add to, and its
+// four fields on any of their argument blocks.
+struct HostList { uint8_t* flag = nullptr; uint32_t *count = nullptr, *list = nullptr; uint32_t cap = 0; };
+template <class Args>
+void set_host_list(Args& a, const HostList& h) {
+  a.host_flag = h.flag;
+  a.host_count = h.count;
+  a.host_list = h.list;
+  a.host_cap = h.cap;
+}
+
+// What the other two need of the decoder's file (otlp_host.cpp).
 // span refs and the scopes' span0 / header / schema refs back to the host
 int layout_to_host(OtlpBatchImpl* b, hipStream_t st);
+// an arena of at least `want` bytes: when it grows, the first `keep` bytes move with it
+int regrow_arena(OtlpBatchImpl* b, size_t keep, size_t want, hipStream_t st);
+// Engine option otlp_condattr (otlp_condattr_host.cpp), called by decode():
+// the stage's span columns behind the span kernels, and the rest after the
+// host pass (`list`: its spans, `host_list` the same on the device).
+int condattr_spans(Engine* e, OtlpBatchImpl* b, uint64_t n, const uint64_t* span_ref, const HostList& hl,
+                   hipStream_t st);
+int condattr_finish(Engine* e, OtlpBatchImpl* b, const uint8_t* pb, const std::vector<uint32_t>& list,
+                    const uint32_t* host_list, hipStream_t st);
 // The host walk of `pb` with a default columniser context (the CPU test
 // seams): the span refs, the layout, and pdata's size of every span as the
 // decoder would compute it.  OSE_EINVAL on a malformed message.

@@ -43,13 +43,12 @@ int encode_gpu(OtlpBatchImpl* b, const ose_outputs* outs, bool sampled, bool tmp
   // workspace
   EncArgs a{};
   const size_t blob = router ? router->dev_blob.size() : 0;
-  struct Part { void** dst; size_t bytes; };
   uint64_t* flags64 = nullptr;
   uint32_t *scope_span0 = nullptr, *res_scope0 = nullptr;
   uint64_t *scope_hdr = nullptr, *scope_schema = nullptr, *res_ref = nullptr;
   uint8_t* routes = nullptr;
   uint64_t* out_base = nullptr;
-  std::vector<Part> parts = {
+  std::vector<SlabPart> parts = {
       {(void**)&a.span_out, 4 * n},
       {(void**)&a.scope_body, 8 * S},
       {(void**)&a.res_body, 8 * R},
@@ -83,15 +82,8 @@ int encode_gpu(OtlpBatchImpl* b, const ose_outputs* outs, bool sampled, bool tmp
     parts.push_back({(void**)&res_ref, 8 * R});
     parts.push_back({(void**)&res_scope0, 4 * R});
   }
-  size_t total = 0;
-  for (auto& p : parts) total = up(total + p.bytes + 16);
   int rc;
-  if ((rc = b->eslab.need(total))) return rc;
-  size_t off = 0;
-  for (auto& p : parts) {
-    *p.dst = b->eslab.p + off;
-    off = up(off + p.bytes + 16);
-  }
+  if ((rc = slab_place(b->eslab, parts))) return rc;
   // host-side uploads through pinned staging: route table, layout, offsets
   size_t hbytes = 64 + 16 * (size_t)n_out + 8 * (size_t)n_out + 16 + blob + 16;
   if (up_scopes) hbytes += 20 * S + 64;

@@ -1,25 +1,30 @@
 // otlp_host.cpp — OTLP protobuf ingest: ose_otlp_decode, the
 // batch's accessors and its release.  The batch type is in otlp_batch.hpp; the
-// way back to bytes (ose_otlp_encode*) is otlp_encode_host.cpp.
+// way back to bytes (ose_otlp_encode*) is otlp_encode_host.cpp, the engine
+// option otlp_condattr's columns are otlp_condattr_host.cpp.  Every device
+// slab is laid out by slab.hpp's carver.
 //
-// One call turns a serialized TracesData into device columns:
-//   1. the bytes go to pinned staging and H2D (the arena: strings are
-//      referenced in place) while the host walks the structure (otlp_pb.cpp
-//      pb_walk: ResourceSpans / ScopeSpans headers, resource and scope
-//      contents, one header per span);
-//   2. per-resource and per-scope columns on the host (columnize.cpp: the
-//      service ids, include/exclude, attribute sets, the fixed sizes);
-//   3. otlp_span_kernel decodes every span on the GPU; under the engine option
-//      otlp_sqlop, otlp_sqlop_kernel then reads db.query.text /
+// One call turns a serialized TracesData into device columns; decode() is
+// these steps, a function each:
+//   1. upload_message: the bytes go to pinned staging and H2D (the arena:
+//      strings are referenced in place);
+//   2. walk_records, walk_scopes: meanwhile the structure is walked
+//      (ResourceSpans / ScopeSpans headers, resource and scope contents, one
+//      header per span) by the host (walk: otlp_pb.cpp's reader, the resources'
+//      and scopes' columns from columnize.cpp) or, below the TracesData chain,
+//      on the GPU (res_walk_gpu, scope_walk_gpu); column_slab lays the device
+//      columns out and uploads the host's;
+//   3. span_kernels: otlp_span_kernel decodes every span on the GPU; under the
+//      engine option otlp_sqlop, otlp_sqlop_kernel then reads db.query.text /
 //      db.operation.name (db_flags, db_query) and may add spans to the list;
 //      under otlp_condattr, otlp_condattr_kernel reads the first KeyValue of
 //      each odigosconditionalattributes key (ose_otlp_condattr_columns) and may
 //      add spans too;
-//   4. the spans they list get the host pass: pb_span + columnize_span, their
-//      strings appended after the message bytes, written by otlp_fix_kernel
-//      (and otlp_sqlop_fix_kernel, otlp_condattr_fix_kernel); under
-//      otlp_condattr the per-scope and per-resource columns of that stage are
-//      then made on the host (condattr_finish).
+//   4. host_pass: the spans they list get pb_span + columnize_span, their
+//      strings appended after the message bytes (regrow_arena), written by
+//      otlp_fix_kernel (and otlp_sqlop_fix_kernel); under otlp_condattr that
+//      stage's entries of the listed spans and its per-scope and per-resource
+//      columns are then made on the host (condattr_finish).
 #include <algorithm>
 #include <chrono>
 #include <deque>
@@ -320,8 +325,12 @@ void host_rule_words(const AttrPlan& p, uint64_t word, std::vector<uint64_t>& ou
 // A resource's columns from its Resource field(s) (merged as pdata merges
 // them), entered into the cache by message bytes when there is at most one
 // field.  False: a malformed Resource.
-bool resolve_resource(const ColumnizeCtx& ctx, ResCache& cache, const uint8_t* p,
-                      const std::vector<std::pair<size_t, size_t>>& resf, ProtoSizer& sizer, CachedRes& cr) {
+using FieldRefs = std::vector<std::pair<size_t, size_t>>;   // (offset in the message, length)
+std::string_view res_key(const uint8_t* p, const FieldRefs& resf) {   // the cache key: the one Resource field's bytes
+  return resf.size() == 1 ? std::string_view((const char*)p + resf[0].first, resf[0].second) : std::string_view();
+}
+bool resolve_resource(const ColumnizeCtx& ctx, ResCache& cache, const uint8_t* p, const FieldRefs& resf,
+                      ProtoSizer& sizer, CachedRes& cr) {
   AttrMap attrs;
   uint32_t dropped = 0;
   for (auto& x : resf)
@@ -333,8 +342,7 @@ bool resolve_resource(const ColumnizeCtx& ctx, ResCache& cache, const uint8_t* p
   cr.sql_ok = rc.sql_ok;
   cr.attr_res = host_rule_word(ctx.attr_plan, rc.attr_res);   // <= 64 json rules (otlp_engine)
   cr.rpart = (uint32_t)flen(sizer.attrs(attrs, 1) + (dropped ? 1 + sov64(dropped) : 0));   // Resource: always emitted
-  const std::string_view key = resf.size() == 1 ? std::string_view((const char*)p + resf[0].first, resf[0].second)
-                                                : std::string_view();
+  const std::string_view key = res_key(p, resf);
   std::unique_lock<std::shared_mutex> g(cache.mu);
   cr.set = cache.intern(rc.attrset);
   if (resf.size() <= 1 && cache.map.size() < ResCache::kMaxEntries && !cache.map.count(key)) {
@@ -342,6 +350,44 @@ bool resolve_resource(const ColumnizeCtx& ctx, ResCache& cache, const uint8_t* p
     cache.map.emplace(std::string_view(cache.keys.back()), cr);
   }
   return true;
+}
+
+// ... from the cache (looked up under the shared lock) when there is at most
+// one Resource field, else resolved
+bool cached_resource(const ColumnizeCtx& ctx, ResCache& cache, const uint8_t* p, const FieldRefs& resf,
+                     ProtoSizer& sizer, CachedRes& cr) {
+  if (resf.size() <= 1) {
+    std::shared_lock<std::shared_mutex> g(cache.mu);
+    auto ci = cache.map.find(res_key(p, resf));
+    if (ci != cache.map.end()) {
+      cr = ci->second;
+      return true;
+    }
+  }
+  return resolve_resource(ctx, cache, p, resf, sizer, cr);
+}
+
+// The fields of the ResourceSpans record at [ro, ro + rl): the Resource
+// field(s) into resf and, where asked for, the ScopeSpans (2), the deprecated
+// ones (1000) and the schema_url's length.  False: a malformed record (fields
+// 1 / 2 / 3 / 1000 must be length-delimited).
+bool res_record_fields(const uint8_t* p, size_t ro, size_t rl, FieldRefs& resf, FieldRefs* scopes = nullptr,
+                       FieldRefs* deprecated = nullptr, size_t* schema = nullptr) {
+  PbReader rr(p + ro, rl);
+  resf.clear();
+  uint32_t f, wt;
+  while (rr.more() && rr.tag(f, wt)) {
+    size_t o, l;
+    if (f == 1 || f == 2 || f == 1000 || f == 3) {
+      if (wt != 2 || !rr.bytes(o, l)) { rr.fail(); break; }
+      if (f == 1) resf.emplace_back(ro + o, l);
+      else if (f == 3) { if (schema) *schema = l; }
+      else if (scopes) (f == 2 ? scopes : deprecated)->emplace_back(ro + o, l);
+    } else {
+      rr.skip(wt, f);
+    }
+  }
+  return rr.ok;
 }
 
 // The TracesData records that start in [s, lim) (a record may run past lim:
@@ -385,45 +431,23 @@ void walk_segment(const ColumnizeCtx& ctx, ResCache& cache, const uint8_t* p, si
       c.lay.res_ref.push_back(ro | ((uint64_t)rl << 32));
       continue;
     }
-    PbReader rr(p + ro, rl);
-    resf.clear();
     scopes.clear();
     deprecated.clear();
     size_t schema = 0;
     uint32_t f, wt;
-    while (rr.more() && rr.tag(f, wt)) {
-      size_t o, l;
-      if (f == 1 || f == 2 || f == 1000 || f == 3) {
-        if (wt != 2 || !rr.bytes(o, l)) { rr.fail(); break; }
-        if (f == 1) resf.emplace_back(ro + o, l);
-        else if (f == 3) schema = l;
-        else (f == 2 ? scopes : deprecated).emplace_back(ro + o, l);
-      } else {
-        rr.skip(wt, f);
-      }
+    if (!res_record_fields(p, ro, rl, resf, &scopes, &deprecated, &schema)) {
+      c.err = "OTLP protobuf: malformed ResourceSpans";
+      return;
     }
-    if (!rr.ok) { c.err = "OTLP protobuf: malformed ResourceSpans"; return; }
     if (scopes.empty()) scopes.swap(deprecated);
-    // the resource's columns (cached by its message bytes)
+    // the resource's columns (cached by its message bytes: this call's cache first)
     CachedRes cr{};
-    const std::string_view key = resf.size() == 1 ? std::string_view((const char*)p + resf[0].first, resf[0].second)
-                                                  : std::string_view();
+    const std::string_view key = res_key(p, resf);
     auto it = resf.size() <= 1 ? rcache.find(key) : rcache.end();
-    bool have = false;
     if (it != rcache.end()) {
       cr = it->second;
-      have = true;
-    } else if (resf.size() <= 1) {
-      std::shared_lock<std::shared_mutex> g(cache.mu);
-      auto ci = cache.map.find(key);
-      if (ci != cache.map.end()) {
-        cr = ci->second;
-        have = true;
-        rcache.emplace(key, cr);
-      }
-    }
-    if (!have) {
-      if (!resolve_resource(ctx, cache, p, resf, sizer, cr)) { c.err = "OTLP protobuf: malformed Resource"; return; }
+    } else {
+      if (!cached_resource(ctx, cache, p, resf, sizer, cr)) { c.err = "OTLP protobuf: malformed Resource"; return; }
       if (resf.size() <= 1) rcache.emplace(key, cr);
     }
     const uint32_t rloc = (uint32_t)c.res_svc.size();
@@ -528,40 +552,50 @@ size_t find_start(const uint8_t* p, size_t n, size_t k) {
   return n;
 }
 
-// The TracesData chain alone (the ResourceSpans records), split over threads
-// as walk() does.
-bool walk_chain(const uint8_t* p, size_t n, std::vector<uint64_t>& res_ref, std::string& err) {
+// The segments walked over threads (chain: walk_segment's TracesData chain
+// alone): the records form one chain of lengths, so each thread starts at a
+// speculated record start and walks up to the next thread's; the split is
+// exact iff every thread ends exactly where the next one started (the chain
+// from 0 is unique), else the walk runs again on one thread.
+bool walk_split(const ColumnizeCtx& ctx, ResCache& cache, const uint8_t* p, size_t n, bool gpu_scopes, bool chain,
+                std::vector<WalkChunk>& ch, std::string& err) {
   const size_t kSeg = size_t(256) << 10;
   int T = (int)std::max<size_t>(1, std::min<size_t>({(size_t)parallel_width(), n / kSeg}));
 #if OSE_DIAG
   if (const char* e = getenv("OSE_WALK_THREADS")) T = std::max(1, atoi(e));
 #endif
-  static const ColumnizeCtx no_ctx;
-  static ResCache no_cache;
-  std::vector<WalkChunk> ch;
   for (int attempt = 0; attempt < 2; attempt++) {
     if (attempt) T = 1;
     std::vector<size_t> st((size_t)T + 1, n), en((size_t)T, 0);
     st[0] = 0;
     for (int t = 1; t < T; t++) st[t] = find_start(p, n, n * (size_t)t / (size_t)T);
-    for (int t = T - 1; t >= 1; t--) st[t] = std::min(st[t], st[t + 1]);
+    for (int t = T - 1; t >= 1; t--) st[t] = std::min(st[t], st[t + 1]);   // monotone
     ch.assign((size_t)T, WalkChunk());
-    parallel_run(T, [&](int t) { walk_segment(no_ctx, no_cache, p, n, st[t], st[t + 1], ch[t], &en[t], true, true); });
+    parallel_run(T, [&](int t) { walk_segment(ctx, cache, p, n, st[t], st[t + 1], ch[t], &en[t], gpu_scopes, chain); });
     bool exact = true;
     for (int t = 0; t < T; t++) {
       if (!ch[t].err.empty()) {
         if (t == 0 || attempt) { err = ch[t].err; return false; }
-        exact = false;
+        exact = false;   // a speculated start inside a record: redo
       }
       if (t + 1 < T && en[t] != st[t + 1]) exact = false;
     }
-    if (en[T - 1] != n && ch[T - 1].err.empty()) {
+    if (en[T - 1] != n && ch[T - 1].err.empty()) {   // trailing bytes the segment walker did not reach
       if (attempt || T == 1) { err = "OTLP protobuf: malformed TracesData"; return false; }
       exact = false;
     }
     if (exact) break;
     if (attempt) { err = "OTLP protobuf: malformed TracesData"; return false; }
   }
+  return true;
+}
+
+// The TracesData chain alone (the ResourceSpans records).
+bool walk_chain(const uint8_t* p, size_t n, std::vector<uint64_t>& res_ref, std::string& err) {
+  static const ColumnizeCtx no_ctx;
+  static ResCache no_cache;
+  std::vector<WalkChunk> ch;
+  if (!walk_split(no_ctx, no_cache, p, n, true, true, ch, err)) return false;
   size_t total = 0;
   for (auto& c : ch) total += c.lay.res_ref.size();
   res_ref.resize(total);
@@ -573,41 +607,10 @@ bool walk_chain(const uint8_t* p, size_t n, std::vector<uint64_t>& res_ref, std:
   return true;
 }
 
-// The walk, split over threads: the records form one chain of lengths, so
-// each thread starts at a speculated record start and walks up to the next
-// thread's; the split is exact iff every thread ends exactly where the next
-// one started (the chain from 0 is unique), else the walk runs again on one
-// thread.
+// The whole walk: walk_split's chunks merged.
 bool walk(const ColumnizeCtx& ctx, ResCache& cache, const uint8_t* p, size_t n, Walked& w, bool gpu_scopes = false) {
-  const size_t kSeg = size_t(256) << 10;
-  int T = (int)std::max<size_t>(1, std::min<size_t>({(size_t)parallel_width(), n / kSeg}));
-#if OSE_DIAG
-  if (const char* e = getenv("OSE_WALK_THREADS")) T = std::max(1, atoi(e));
-#endif
   std::vector<WalkChunk> ch;
-  for (int attempt = 0; attempt < 2; attempt++) {
-    if (attempt) T = 1;
-    std::vector<size_t> st((size_t)T + 1, n), en((size_t)T, 0);
-    st[0] = 0;
-    for (int t = 1; t < T; t++) st[t] = find_start(p, n, n * (size_t)t / (size_t)T);
-    for (int t = T - 1; t >= 1; t--) st[t] = std::min(st[t], st[t + 1]);   // monotone
-    ch.assign((size_t)T, WalkChunk());
-    parallel_run(T, [&](int t) { walk_segment(ctx, cache, p, n, st[t], st[t + 1], ch[t], &en[t], gpu_scopes); });
-    bool exact = true;
-    for (int t = 0; t < T; t++) {
-      if (!ch[t].err.empty()) {
-        if (t == 0 || attempt) { w.err = ch[t].err; return false; }
-        exact = false;   // a speculated start inside a record: redo
-      }
-      if (t + 1 < T && en[t] != st[t + 1]) exact = false;
-    }
-    if (en[T - 1] != n && ch[T - 1].err.empty()) {   // trailing bytes the segment walker did not reach
-      if (attempt || T == 1) { w.err = "OTLP protobuf: malformed TracesData"; return false; }
-      exact = false;
-    }
-    if (exact) break;
-    if (attempt) { w.err = "OTLP protobuf: malformed TracesData"; return false; }
-  }
+  if (!walk_split(ctx, cache, p, n, gpu_scopes, false, ch, w.err)) return false;
   // merge: global indices, attribute sets in first-appearance order
   std::unordered_map<uint32_t, uint32_t> set_map;   // cache id -> this batch's
   {
@@ -709,10 +712,18 @@ int otlp_host_walk_sizes(const uint8_t* pb, size_t len, std::vector<uint64_t>& s
 }
 
 namespace {
-// The GPU half of the structural walk: every ScopeSpans the host did not
-// walk is counted, sized and listed on the device (otlp_scope_*_kernel);
-// returns the span count in *n_out, or 1 in *redo when some scope needs the
-// host walk (groups or a malformed field: the caller walks on the host).
+// A look-back scan of n counts (launch_scan_u32; none when n is 0).  `status`
+// and `words` are zeroed by the caller, which names the words the scan's total,
+// tile counter and error go to and reads them back by those indices.
+int scan_counts(uint64_t n, uint32_t tiles, const uint32_t* in, uint32_t* out, uint64_t* status, uint32_t* words,
+                int total, int counter, int error, hipStream_t st) {
+  // (n, n_tiles, popcount, gate, in, out, total, counter, status, error)
+  const ScanArgs sa{n, tiles, 0, nullptr, in, out, words + total, words + counter, status, words + error};
+  if (n) launch_scan_u32(sa, st);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 // The GPU half of the ResourceSpans level: the host walks
 // the TracesData chain only (walk_chain), the device each record's fields
 // (otlp_res_fields_kernel), the Resource columns from the device resource
@@ -807,11 +818,10 @@ int res_walk_gpu(OtlpEngine* o, OtlpBatchImpl* b, const uint8_t* pb, size_t len,
   b->walk_info[0] = gpu_chain ? 1u : 0u;
   const uint64_t RN = std::max<uint64_t>(R, 1);
   const uint32_t tiles = (uint32_t)((RN + kScanTileItems - 1) / kScanTileItems);
-  struct Part { void** dst; size_t bytes; };
   OtlpResArgs a{};
   uint64_t* status = nullptr;
   uint32_t* words = nullptr;
-  const std::vector<Part> parts = {
+  const std::vector<SlabPart> parts = {
       {(void**)&a.res_ref, 8 * RN}, {(void**)&a.flags, 4 * RN}, {(void**)&a.nscope, 4 * RN},
       {(void**)&a.schema_len, 4 * RN}, {(void**)&a.scope0, 4 * RN}, {(void**)&a.res_svc, 4 * RN},
       {(void**)&a.res_svc_str, 4 * RN}, {(void**)&a.res_set, 4 * RN}, {(void**)&a.res_size, 4 * RN},
@@ -819,14 +829,7 @@ int res_walk_gpu(OtlpEngine* o, OtlpBatchImpl* b, const uint8_t* pb, size_t len,
       {(void**)&a.miss_list, 4 * RN},
       {(void**)&status, 8 * (size_t)tiles + 64}, {(void**)&words, 64},
   };
-  size_t total = 0;
-  for (auto& p : parts) total = up(total + p.bytes + 16);
-  if ((rc = b->rslab.need(total)) || (rc = b->stage.need(std::max<size_t>(8 * RN, 12 * (size_t)T) + 64))) return rc;
-  size_t off = 0;
-  for (auto& p : parts) {
-    *p.dst = b->rslab.p + off;
-    off = up(off + p.bytes + 16);
-  }
+  if ((rc = slab_place(b->rslab, parts)) || (rc = b->stage.need(std::max<size_t>(8 * RN, 12 * (size_t)T) + 64))) return rc;
   if (!sql) a.res_sql_ok = nullptr;
   if (gpu_chain) {   // the records of the linked segments, written on the GPU
     std::memcpy(b->stage.p, seg_first.data(), 8 * (size_t)T);
@@ -860,17 +863,7 @@ int res_walk_gpu(OtlpEngine* o, OtlpBatchImpl* b, const uint8_t* pb, size_t len,
     (void)hipGetLastError();
     launch_otlp_res_fields(a, st);
     HIP_TRY(hipGetLastError());
-    ScanArgs sa{};
-    sa.n = R;
-    sa.n_tiles = tiles;
-    sa.in = a.nscope;
-    sa.out = const_cast<uint32_t*>(a.scope0);
-    sa.total = words + 2;
-    sa.counter = words + 3;
-    sa.status = status;
-    sa.error = words + 4;
-    if (R) launch_scan_u32(sa, st);
-    HIP_TRY(hipGetLastError());
+    if ((rc = scan_counts(R, tiles, a.nscope, const_cast<uint32_t*>(a.scope0), status, words, 2, 3, 4, st))) return rc;
     HIP_TRY(hipMemcpyAsync(h, words, 12, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
   }
@@ -897,33 +890,12 @@ int res_walk_gpu(OtlpEngine* o, OtlpBatchImpl* b, const uint8_t* pb, size_t len,
       for (uint32_t k = (uint32_t)((uint64_t)nm * t / T); k < (uint32_t)((uint64_t)nm * (t + 1) / T); k++) {
         const uint32_t r = miss[k];
         const uint64_t rr = w.lay.res_ref[r];
-        const size_t ro = (uint32_t)rr;
-        PbReader rd(pb + ro, (size_t)(rr >> 32));
-        resf.clear();
-        uint32_t f, wt;
-        while (rd.more() && rd.tag(f, wt)) {
-          size_t fo, fl;
-          if (f == 1 || f == 2 || f == 3 || f == 1000) {
-            if (wt != 2 || !rd.bytes(fo, fl)) { rd.fail(); break; }
-            if (f == 1) resf.emplace_back(ro + fo, fl);
-          } else {
-            rd.skip(wt, f);
-          }
+        if (!res_record_fields(pb, (uint32_t)rr, (size_t)(rr >> 32), resf)) {
+          errs[t] = "OTLP protobuf: malformed ResourceSpans";
+          return;
         }
-        if (!rd.ok) { errs[t] = "OTLP protobuf: malformed ResourceSpans"; return; }
         CachedRes cr{};
-        bool have = false;
-        const std::string_view key = resf.size() == 1 ? std::string_view((const char*)pb + resf[0].first, resf[0].second)
-                                                      : std::string_view();
-        if (resf.size() <= 1) {
-          std::shared_lock<std::shared_mutex> g(o->res_cache.mu);
-          auto ci = o->res_cache.map.find(key);
-          if (ci != o->res_cache.map.end()) {
-            cr = ci->second;
-            have = true;
-          }
-        }
-        if (!have && !resolve_resource(o->ctx, o->res_cache, pb, resf, sizer, cr)) {
+        if (!cached_resource(o->ctx, o->res_cache, pb, resf, sizer, cr)) {
           errs[t] = "OTLP protobuf: malformed Resource";
           return;
         }
@@ -974,17 +946,7 @@ int res_walk_gpu(OtlpEngine* o, OtlpBatchImpl* b, const uint8_t* pb, size_t len,
   HIP_TRY(hipMemsetAsync(sstat, 0, o_words + 64 - o_stat, st));
   launch_otlp_set_first(a.res_set, R, first, is_first, st);
   HIP_TRY(hipGetLastError());
-  ScanArgs ss{};
-  ss.n = R;
-  ss.n_tiles = tiles;
-  ss.in = is_first;
-  ss.out = pos;
-  ss.total = swords + 1;
-  ss.counter = swords + 2;
-  ss.status = sstat;
-  ss.error = swords;
-  if (R) launch_scan_u32(ss, st);
-  HIP_TRY(hipGetLastError());
+  if ((rc = scan_counts(R, tiles, is_first, pos, sstat, swords, 1, 2, 0, st))) return rc;
   launch_otlp_set_apply(a.res_set, R, first, is_first, pos, list, st);
   HIP_TRY(hipGetLastError());
   // the scan's words and the batch's set ids come back behind the scope
@@ -1010,6 +972,10 @@ int res_sets_finish(OtlpEngine* o, OtlpBatchImpl* b, Walked& w, hipStream_t st) 
   return 0;
 }
 
+// The GPU half of the structural walk: every ScopeSpans the host did not
+// walk is counted, sized and listed on the device (otlp_scope_*_kernel);
+// returns the span count in *n_out, or 1 in *redo when some scope needs the
+// host walk (groups or a malformed field: the caller walks on the host).
 // res: the GPU ResourceSpans pass ran (res_walk_gpu): its S scopes are listed
 // on the device by otlp_res_scopes_kernel, every one walked here
 int scope_walk_gpu(Engine* e, OtlpBatchImpl* b, Walked& w, hipStream_t st, uint64_t* n_out, bool* redo,
@@ -1018,43 +984,32 @@ int scope_walk_gpu(Engine* e, OtlpBatchImpl* b, Walked& w, hipStream_t st, uint6
   const uint64_t S = res ? S_res : w.scope_size.size(), H = res ? 0 : w.span_ref.size();
   *redo = false;
   const uint32_t tiles = (uint32_t)((S + kScanTileItems - 1) / kScanTileItems);
-  struct Part { void** dst; size_t bytes; const void* src; };
   uint64_t *scope_ref, *hdr, *schema, *host_at, *host_refs, *status;
   uint8_t* on_host;
   uint32_t *count, *scope_size, *flags, *span0, *scope_res, *words;
-  std::vector<Part> parts = {
+  const std::vector<SlabPart> parts = {
       {(void**)&scope_ref, 8 * S, res ? nullptr : b->lay.scope_ref.data()},
       {(void**)&hdr, 8 * S, res ? nullptr : b->lay.scope_hdr.data()},
       {(void**)&schema, 8 * S, res ? nullptr : b->lay.scope_schema.data()},
-      {(void**)&host_at, 8 * S, nullptr},
+      {(void**)&host_at, 8 * S, nullptr, !res},   // filled in staging below
       {(void**)&host_refs, 8 * H, res ? nullptr : w.span_ref.data()},
       {(void**)&on_host, S, res ? nullptr : w.scope_on_host.data()},
       {(void**)&count, 4 * S, res ? nullptr : w.scope_count.data()},
       {(void**)&scope_size, 4 * S, res ? nullptr : w.scope_size.data()},
       {(void**)&scope_res, 4 * S, res ? nullptr : w.scope_res.data()},
       // device-only
-      {(void**)&flags, 4 * S, nullptr},
-      {(void**)&span0, 4 * S, nullptr},
-      {(void**)&status, 8 * (size_t)tiles + 64, nullptr},
-      {(void**)&words, 64, nullptr},
+      {(void**)&flags, 4 * S},
+      {(void**)&span0, 4 * S},
+      {(void**)&status, 8 * (size_t)tiles + 64},
+      {(void**)&words, 64},
   };
-  size_t total = 0, inputs = 0;
-  for (auto& p : parts) {
-    total = up(total + p.bytes + 16);
-    if (!res && (p.src || p.dst == (void**)&host_at)) inputs = total;
-  }
+  SlabSize z;
   int rc;
-  if ((rc = b->sslab.need(total)) || (rc = b->stage.need(inputs))) return rc;
-  size_t off = 0;
-  for (auto& p : parts) {
-    *p.dst = b->sslab.p + off;
-    if (!res && p.src && p.bytes) std::memcpy(b->stage.p + off, p.src, p.bytes);
-    off = up(off + p.bytes + 16);
-  }
+  if ((rc = slab_place(b->sslab, parts, &b->stage, &z))) return rc;
   if (!res) {   // host_at: the host-walked scopes' offsets into host_refs (the walk's span0)
     uint64_t* ha = reinterpret_cast<uint64_t*>(b->stage.p + (reinterpret_cast<uint8_t*>(host_at) - b->sslab.p));
     for (uint64_t q = 0; q < S; q++) ha[q] = b->lay.scope_span0[q];
-    HIP_TRY(hipMemcpyAsync(b->sslab.p, b->stage.p, inputs, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b->sslab.p, b->stage.p, z.inputs, hipMemcpyHostToDevice, st));
   } else {
     // the scopes of every resource at their place, none walked on the host
     HIP_TRY(hipMemsetAsync(on_host, 0, S, st));
@@ -1065,7 +1020,7 @@ int scope_walk_gpu(Engine* e, OtlpBatchImpl* b, Walked& w, hipStream_t st, uint6
     b->d_scope_ref = scope_ref;
   }
   const size_t dev0 = reinterpret_cast<uint8_t*>(flags) - b->sslab.p;
-  HIP_TRY(hipMemsetAsync(flags, 0, total - dev0, st));   // flags, span0, scan status, words
+  HIP_TRY(hipMemsetAsync(flags, 0, z.total - dev0, st));   // flags, span0, scan status, words
   OtlpScopeArgs a{};
   a.pb = b->arena.p;
   a.n_scopes = S;
@@ -1084,17 +1039,7 @@ int scope_walk_gpu(Engine* e, OtlpBatchImpl* b, Walked& w, hipStream_t st, uint6
   (void)hipGetLastError();
   launch_otlp_scope_count(a, st);
   HIP_TRY(hipGetLastError());
-  ScanArgs sa{};
-  sa.n = S;
-  sa.n_tiles = tiles;
-  sa.in = count;
-  sa.out = span0;
-  sa.total = words + 1;
-  sa.counter = words + 2;
-  sa.status = status;
-  sa.error = words;
-  if (S) launch_scan_u32(sa, st);
-  HIP_TRY(hipGetLastError());
+  if ((rc = scan_counts(S, tiles, count, span0, status, words, 1, 2, 0, st))) return rc;
   uint32_t h[2] = {0, 0};
   HIP_TRY(hipMemcpyAsync(h, words, 8, hipMemcpyDeviceToHost, st));
   // which scopes the host must finish (flags): copied back with the counts
@@ -1183,304 +1128,51 @@ int layout_to_host(OtlpBatchImpl* b, hipStream_t st) {
   return 0;
 }
 
+// (walk_info[7] says that the arena was regrown)
+int regrow_arena(OtlpBatchImpl* b, size_t keep, size_t want, hipStream_t st) {
+  if (want <= b->arena.cap) return 0;
+  DevBuf bigger;
+  if (int rc = bigger.need(want)) return rc;
+  HIP_TRY(hipMemcpyAsync(bigger.p, b->arena.p, keep, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));   // the old arena is freed on return
+  std::swap(b->arena.p, bigger.p);
+  std::swap(b->arena.cap, bigger.cap);
+  b->cols.arena = b->arena.p;
+  b->walk_info[7] = 1;
+  return 0;
+}
+
 namespace {
-// ---- engine option otlp_condattr: odigosconditionalattributes' columns ----------
-// The span columns on the GPU: the batch's slab of them, span_has zeroed,
-// otlp_condattr_kernel behind the span kernel (before the host-pass count is
-// read back: the kernel may add to the list).
-int condattr_spans(Engine* e, OtlpBatchImpl* b, uint64_t n, const uint64_t* span_ref, uint8_t* host_flag,
-                   uint32_t* host_count, uint32_t* host_list, hipStream_t st) {
-  const size_t K = e->condattr_tab.keys.size();
-  const ose_columns& c = b->cols;
-  const size_t N = std::max<uint64_t>(n, 1), S = std::max<uint32_t>(c.n_scopes, 1), R = std::max<uint32_t>(c.n_resources, 1);
-  ose_condattr_columns& ca = b->ca;
-  ca = ose_condattr_columns{};
-  struct Part { void** dst; size_t bytes; };
-  const Part parts[] = {
-      {(void**)&ca.span_has, K * N}, {(void**)&ca.span_val, 8 * K * N}, {(void**)&ca.span_kv_size, 4 * K * N},
-      {(void**)&ca.scope_name, 8 * S}, {(void**)&ca.scope_has, K * S}, {(void**)&ca.scope_val, 8 * K * S},
-      {(void**)&ca.res_has, K * R}, {(void**)&ca.res_val, 8 * K * R},
-  };
-  size_t total = 0;
-  for (auto& p : parts) total = up(total + p.bytes + 16);
-  int rc;
-  if ((rc = b->caslab.need(total))) return rc;
-  size_t off = 0;
-  for (auto& p : parts) {
-    *p.dst = b->caslab.p + off;
-    off = up(off + p.bytes + 16);
-  }
-  b->ca_keys = (uint32_t)K;
-  if (!n || !K) return 0;
-  HIP_TRY(hipMemsetAsync(const_cast<uint8_t*>(ca.span_has), 0, K * N, st));
-  OtlpCondAttrArgs a{};
-  a.pb = b->arena.p;
-  a.n_spans = n;
-  a.span_ref = span_ref;
-  a.blob = e->condattr_blob_dev;
-  a.slots = static_cast<const OtlpCaSlot*>(e->condattr_slots_dev);
-  a.slot_mask = e->condattr_slot_mask;
-  a.key_lens = e->condattr_key_lens;
-  a.span_has = const_cast<uint8_t*>(ca.span_has);
-  a.span_val = const_cast<ose_strref*>(ca.span_val);
-  a.span_kv_size = const_cast<uint32_t*>(ca.span_kv_size);
-  a.host_flag = host_flag;
-  a.host_count = host_count;
-  a.host_list = host_list;
-  a.host_cap = (uint32_t)N;
-  Engine::Timed tm{};
-  e->prof_begin("otlp_condattr_kernel", st, tm);
-  launch_otlp_condattr(a, st);
-  HIP_TRY(hipGetLastError());
-  e->prof_end(tm, st);
-  return 0;
+// ---- ose_otlp_decode's steps (decode() below calls them in this order) ----------
+// the span columns as the span kernel and the host pass's fix kernel write them
+template <class Args>
+void set_span_columns(Args& a, const ose_columns& c) {
+  a.tid = const_cast<uint64_t*>(c.trace_id);
+  a.start = const_cast<uint64_t*>(c.start_ns);
+  a.end = const_cast<uint64_t*>(c.end_ns);
+  a.status = const_cast<uint8_t*>(c.status);
+  a.kind = const_cast<uint8_t*>(c.kind);
+  a.url_flags = const_cast<uint8_t*>(c.url_flags);
+  a.path = const_cast<ose_strref*>(c.path);
+  a.route = const_cast<ose_strref*>(c.route);
+  a.span_size = const_cast<uint32_t*>(c.span_size);
+  a.name_len = const_cast<uint32_t*>(c.name_len);
+  a.attr_match = const_cast<uint64_t*>(c.attr_match);
+  a.attr_type = const_cast<uint8_t*>(c.attr_type);
+  a.attr_val = const_cast<uint64_t*>(c.attr_val);
 }
 
-// The rest, after the host pass: the K entries of every listed span (pb_span
-// and the columniser's lookup, written by otlp_condattr_fix_kernel), and the
-// per-scope and per-resource columns, made on the host from the message bytes
-// at the scopes' InstrumentationScope refs and the resources' Resource fields
-// (S and R are small against N; equal header bytes are looked up once).  The
-// strings go after the arena's bytes (the message, then the host pass's
-// strings); the arena is regrown when they do not fit.
-int condattr_finish(Engine* e, OtlpBatchImpl* b, const uint8_t* pb, const std::vector<uint32_t>& list,
-                    const uint32_t* host_list, hipStream_t st) {
-  const std::vector<std::string>& keys = e->condattr_tab.keys;
-  const size_t K = keys.size();
-  ose_columns& c = b->cols;
-  const uint64_t n = c.n_spans, S = c.n_scopes, R = c.n_resources;
-  const size_t cnt = list.size();
-  // the scopes' and resources' refs: on the host already, or fetched (these
-  // three arrays only: the span refs stay on the device)
-  std::vector<uint64_t> hdr_d, sref_d, rref_d;
-  const uint64_t *hdr = b->lay.scope_hdr.data(), *sref = b->lay.scope_ref.data(), *rref = b->lay.res_ref.data();
-  if (!b->layout_on_host) {
-    hdr_d.resize(S);
-    if (S) HIP_TRY(hipMemcpyAsync(hdr_d.data(), b->d_hdr, 8 * S, hipMemcpyDeviceToHost, st));
-    hdr = hdr_d.data();
-    if (b->res_on_device) {
-      sref_d.resize(S);
-      rref_d.resize(R);
-      if (S) HIP_TRY(hipMemcpyAsync(sref_d.data(), b->d_scope_ref, 8 * S, hipMemcpyDeviceToHost, st));
-      if (R) HIP_TRY(hipMemcpyAsync(rref_d.data(), b->d_res_ref, 8 * R, hipMemcpyDeviceToHost, st));
-      sref = sref_d.data();
-      rref = rref_d.data();
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-  }
-  // behind the host pass's strings, or, without any, behind the message's 16
-  // zero bytes of slack, where the host pass's would start
-  const size_t base = std::max<size_t>(c.arena_bytes, up(b->pb_len + 16, 16));
-  std::string strs;
-  ProtoSizer sizer;
-  auto pad = [](size_t x) { return std::max<size_t>(x, 1); };
-  std::vector<uint8_t> fix_has(pad(K * cnt), 0), scope_has(pad(K * S), 0), res_has(pad(K * R), 0);
-  std::vector<ose_strref> fix_val(pad(K * cnt), ose_strref{0, 0}), scope_val(pad(K * S), ose_strref{0, 0}),
-      res_val(pad(K * R), ose_strref{0, 0}), scope_name(pad(S), ose_strref{0, 0});
-  std::vector<uint32_t> fix_kv(pad(K * cnt), 0);
-  for (size_t q = 0; q < cnt; q++) {
-    const uint64_t ref = b->span_ref[list[q]];   // (the host pass brought the layout back)
-    Span sp;
-    if (!pb_span(pb + (uint32_t)ref, (size_t)(ref >> 32), sp)) return fail(OSE_EINVAL, "OTLP protobuf: malformed Span");
-    condattr_lookup(keys, sp.attrs, q, cnt, strs, base, sizer, fix_has.data(), fix_val.data(), fix_kv.data());
-  }
-  auto copy_row = [&](std::vector<uint8_t>& has, std::vector<ose_strref>& val, size_t rows, size_t from, size_t to) {
-    for (size_t k = 0; k < K; k++) {
-      has[k * rows + to] = has[k * rows + from];
-      val[k * rows + to] = val[k * rows + from];
-    }
-  };
-  // The scopes and the resources, split over threads (a node's batch may hold
-  // a scope for every few spans): each thread looks equal header bytes up once,
-  // collects its strings with refs relative to them, and the refs are moved to
-  // the strings' final place once every thread's share is known.
-  const int T = (int)std::min<uint64_t>((uint64_t)std::max(1, parallel_width()), std::max<uint64_t>(1, (S + R) / 4096));
-  struct Share { std::string strs, err; };
-  std::vector<Share> share((size_t)T);
-  auto scopes_of = [&](Share& me, size_t s_lo, size_t s_hi) {
-    std::unordered_map<std::string_view, size_t> seen;
-    for (size_t s = s_lo; s < s_hi; s++) {
-      const uint64_t h = hdr[s];
-      ScopeSpans meta;
-      if (h != OtlpLayout::kMulti) {
-        const std::string_view key((const char*)pb + (uint32_t)h, (size_t)(h >> 32));
-        auto it = seen.find(key);
-        if (it != seen.end()) {
-          scope_name[s] = scope_name[it->second];
-          copy_row(scope_has, scope_val, S, it->second, s);
-          continue;
-        }
-        seen.emplace(key, s);
-        if (!pb_scope(pb + (uint32_t)h, (size_t)(h >> 32), meta)) { me.err = "OTLP protobuf: malformed InstrumentationScope"; return; }
-      } else {   // several scope fields: merged, as the encoder's scope_header does
-        const uint64_t sr = sref[s];
-        PbReader r(pb + (uint32_t)sr, (size_t)(sr >> 32));
-        uint32_t f, wt;
-        while (r.more() && r.tag(f, wt)) {
-          size_t o, l;
-          if (f == 1 && wt == 2 && r.bytes(o, l)) {
-            if (!pb_scope(pb + (uint32_t)sr + o, l, meta)) { me.err = "OTLP protobuf: malformed InstrumentationScope"; return; }
-          } else if (f != 1) {
-            r.skip(wt, f);
-          } else {
-            r.fail();
-          }
-        }
-        if (!r.ok) { me.err = "OTLP protobuf: malformed ScopeSpans"; return; }
-      }
-      scope_name[s] = ose_strref{(uint32_t)me.strs.size(), (uint32_t)meta.scope_name.size()};
-      me.strs += meta.scope_name;
-      condattr_lookup(keys, meta.scope_attrs, s, S, me.strs, 0, sizer, scope_has.data(), scope_val.data(), nullptr);
-    }
-  };
-  auto resources_of = [&](Share& me, size_t r_lo, size_t r_hi) {
-    std::unordered_map<std::string_view, size_t> seen;
-    std::vector<std::pair<size_t, size_t>> rf;   // the Resource fields (merged when several)
-    for (size_t ri = r_lo; ri < r_hi; ri++) {
-      const size_t ro = (uint32_t)rref[ri], rl = (size_t)(rref[ri] >> 32);
-      PbReader p(pb + ro, rl);
-      rf.clear();
-      uint32_t f, wt;
-      while (p.more() && p.tag(f, wt)) {
-        size_t o, l;
-        if (wt == 2 && f == 1) {
-          if (!p.bytes(o, l)) break;
-          rf.emplace_back(ro + o, l);
-        } else {
-          p.skip(wt, f);
-        }
-      }
-      if (!p.ok) { me.err = "OTLP protobuf: malformed ResourceSpans"; return; }
-      if (rf.size() == 1) {
-        const std::string_view key((const char*)pb + rf[0].first, rf[0].second);
-        auto it = seen.find(key);
-        if (it != seen.end()) {
-          copy_row(res_has, res_val, R, it->second, ri);
-          continue;
-        }
-        seen.emplace(key, ri);
-      }
-      AttrMap attrs;
-      uint32_t dropped = 0;
-      for (auto& x : rf)
-        if (!pb_resource(pb + x.first, x.second, attrs, dropped)) { me.err = "OTLP protobuf: malformed Resource"; return; }
-      condattr_lookup(keys, attrs, ri, R, me.strs, 0, sizer, res_has.data(), res_val.data(), nullptr);
-    }
-  };
-  parallel_run(T, [&](int t) {
-    scopes_of(share[(size_t)t], S * t / T, S * (t + 1) / T);
-    if (share[(size_t)t].err.empty()) resources_of(share[(size_t)t], R * t / T, R * (t + 1) / T);
-  });
-  for (auto& sh : share)
-    if (!sh.err.empty()) return fail(OSE_EINVAL, sh.err);
-  std::vector<size_t> share_at((size_t)T);
-  {
-    size_t at = base + strs.size();
-    for (int t = 0; t < T; t++) {
-      share_at[(size_t)t] = at;
-      at += share[(size_t)t].strs.size();
-    }
-    if (at > 0xFFFFFFF0ull) return fail(OSE_ERANGE, "OTLP ingest: the arena passes 4 GiB");
-  }
-  parallel_run(T, [&](int t) {
-    const uint32_t add = (uint32_t)share_at[(size_t)t];
-    for (size_t s = S * t / T; s < S * (t + 1) / T; s++) {
-      scope_name[s].off += add;
-      for (size_t k = 0; k < K; k++)
-        if (scope_has[k * S + s]) scope_val[k * S + s].off += add;
-    }
-    for (size_t ri = R * t / T; ri < R * (t + 1) / T; ri++)
-      for (size_t k = 0; k < K; k++)
-        if (res_has[k * R + ri]) res_val[k * R + ri].off += add;
-  });
-  for (auto& sh : share) strs += sh.strs;
-  const size_t end = base + strs.size();
-  if (end > 0xFFFFFFF0ull) return fail(OSE_ERANGE, "OTLP ingest: the arena passes 4 GiB");
+// 1. the bytes H2D into the arena, zero slack behind them: straight from the
+//    caller's buffer when it is pinned (*pinned), else through pinned staging
+int upload_message(OtlpBatchImpl* b, const uint8_t* pb, size_t len, hipStream_t st, bool* pinned) {
   int rc;
-  if (end + 16 > b->arena.cap) {   // a larger arena: what it holds moves with it
-    DevBuf bigger;
-    if ((rc = bigger.need(end + 16))) return rc;
-    if (base) HIP_TRY(hipMemcpyAsync(bigger.p, b->arena.p, base, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    std::swap(b->arena.p, bigger.p);
-    std::swap(b->arena.cap, bigger.cap);
-    c.arena = b->arena.p;
-    b->walk_info[7] = 1;
-  }
-  ose_condattr_columns& ca = b->ca;
-  auto upl = [&](const void* dst, const void* src, size_t bytes) {
-    return bytes ? hipMemcpyAsync(const_cast<void*>(dst), src, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
-  };
-  HIP_TRY(upl(b->arena.p + base, strs.data(), strs.size()));
-  HIP_TRY(upl(ca.scope_name, scope_name.data(), 8 * S));
-  HIP_TRY(upl(ca.scope_has, scope_has.data(), K * S));
-  HIP_TRY(upl(ca.scope_val, scope_val.data(), 8 * K * S));
-  HIP_TRY(upl(ca.res_has, res_has.data(), K * R));
-  HIP_TRY(upl(ca.res_val, res_val.data(), 8 * K * R));
-  if (cnt && K) {
-    const size_t hb = up(K * cnt + 16), vb = up(8 * K * cnt + 16), kb = up(4 * K * cnt + 16);
-    if ((rc = b->cafix.need(hb + vb + kb))) return rc;
-    HIP_TRY(upl(b->cafix.p, fix_has.data(), K * cnt));
-    HIP_TRY(upl(b->cafix.p + hb, fix_val.data(), 8 * K * cnt));
-    HIP_TRY(upl(b->cafix.p + hb + vb, fix_kv.data(), 4 * K * cnt));
-    OtlpCondAttrFixArgs fa{};
-    fa.cnt = (uint32_t)cnt;
-    fa.n_keys = (uint32_t)K;
-    fa.n_spans = n;
-    fa.list = host_list;
-    fa.fix_has = b->cafix.p;
-    fa.fix_val = reinterpret_cast<const ose_strref*>(b->cafix.p + hb);
-    fa.fix_kv = reinterpret_cast<const uint32_t*>(b->cafix.p + hb + vb);
-    fa.span_has = const_cast<uint8_t*>(ca.span_has);
-    fa.span_val = const_cast<ose_strref*>(ca.span_val);
-    fa.span_kv_size = const_cast<uint32_t*>(ca.span_kv_size);
-    launch_otlp_condattr_fix(fa, st);
-    HIP_TRY(hipGetLastError());
-  }
-  HIP_TRY(hipStreamSynchronize(st));   // the sources are on this stack
-  c.arena_bytes = end;
-  ca.n_spans = n;
-  ca.n_resources = (uint32_t)R;
-  ca.n_scopes = (uint32_t)S;
-  ca.arena_bytes = end;
-  ca.arena = c.arena;
-  ca.scope = c.scope;
-  ca.scope_resource = c.scope_resource;
-  ca.span_size = c.span_size;
-  b->ca_on = true;
-  return 0;
-}
-
-int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchImpl* b, bool host_scopes = false,
-           bool host_res = false) {
-  int rc;
-  OtlpEngine* o = otlp_engine(e, rc);
-  if (!o) return rc;
-  if (len > 0xFFFFFFF0ull) return fail(OSE_ERANGE, "OTLP ingest: message beyond the 4 GiB arena range");
-  using clk = std::chrono::steady_clock;
-  auto t0 = clk::now();
-  auto lap = [&](int k) {
-    const auto t = clk::now();
-    b->t_ms[k] = std::chrono::duration<double, std::milli>(t - t0).count();
-    t0 = t;
-  };
-  for (double& x : b->t_ms) x = 0;
-  for (int k = 0; k < 8; k++)
-    if (k != 4 && k != 5) b->walk_info[k] = 0;   // (the redo flags are the outer call's)
-  // engine option otlp_sqlop: db_flags / db_query / res_sql_ok are decoded too
-  const bool sql = e->has_sqlop && e->option(Engine::kOptOtlpSqlop);
-  // engine option otlp_condattr: odigosconditionalattributes' columns are decoded too
-  const bool ca = e->has_condattr && e->option(Engine::kOptOtlpCondattr);
-  b->ca_on = false;
-  // 1. the bytes H2D (straight from the caller's buffer when it is pinned,
-  //    else through pinned staging), the walk meanwhile
   const size_t pb_cap = up(len + 16, 16);
   const size_t fix_reserve = std::max<size_t>(1 << 16, len / 8);
   if ((rc = b->arena.need(pb_cap + fix_reserve + 16))) return rc;
   hipPointerAttribute_t pa{};
-  const bool pinned = len && hipPointerGetAttributes(&pa, pb) == hipSuccess && pa.type == hipMemoryTypeHost;
+  *pinned = len && hipPointerGetAttributes(&pa, pb) == hipSuccess && pa.type == hipMemoryTypeHost;
   (void)hipGetLastError();   // an unregistered pointer is not an error here
-  if (pinned) {
+  if (*pinned) {
     HIP_TRY(hipMemcpyAsync(b->arena.p, pb, len, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(b->arena.p + len, 0, pb_cap - len, st));
   } else {
@@ -1489,70 +1181,63 @@ int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchIm
     std::memset(b->stage.p + len, 0, pb_cap - len);
     HIP_TRY(hipMemcpyAsync(b->arena.p, b->stage.p, pb_cap, hipMemcpyHostToDevice, st));
   }
-  lap(0);
-  // 2. the walk: TracesData and ResourceSpans on the host, ScopeSpans up to
-  //    64 KB on the GPU (engine option otlp_host_scopes: all on the host)
-  //    (otlp_host_resources: ResourceSpans on the host, ScopeSpans on the
-  //    GPU; without it only the TracesData chain is walked on the host)
-  const bool gpu_scopes = !host_scopes && !e->option(Engine::kOptOtlpHostScopes);
-  const bool gpu_res = gpu_scopes && !host_res && !e->option(Engine::kOptOtlpHostResources);
-  Walked w;
-  OtlpResArgs ra{};
-  uint64_t R = 0, S = 0;
-  if (gpu_res) {
-    bool redo = false;
-    if ((rc = res_walk_gpu(o, b, pb, len, st, w, &R, &S, &ra, &redo, !pinned, sql))) return rc;
-    if (redo) {   // a malformed record: the host walk reports it
-      b->walk_info[5] = 1;
-      return decode(e, pb, len, st, b, false, true);
-    }
-  } else {
-    if (!walk(o->ctx, o->res_cache, pb, len, w, gpu_scopes)) return fail(OSE_EINVAL, w.err);
-    HIP_TRY(hipStreamSynchronize(st));   // the staging buffer is reused below
-    R = w.res_svc.size();
-  }
-  lap(1);
+  return 0;
+}
+
+// 2a. the walk: ResourceSpans on the GPU behind the host's chain walk (gpu_res:
+//     *ra, *R, *S filled; *redo: a malformed record), else the host walk
+int walk_records(OtlpEngine* o, OtlpBatchImpl* b, const uint8_t* pb, size_t len, hipStream_t st, bool gpu_scopes,
+                 bool gpu_res, bool msg_in_stage, bool sql, Walked& w, OtlpResArgs* ra, uint64_t* R, uint64_t* S,
+                 bool* redo) {
+  if (gpu_res) return res_walk_gpu(o, b, pb, len, st, w, R, S, ra, redo, msg_in_stage, sql);
+  if (!walk(o->ctx, o->res_cache, pb, len, w, gpu_scopes)) return fail(OSE_EINVAL, w.err);
+  HIP_TRY(hipStreamSynchronize(st));   // the staging buffer is reused below
+  *R = w.res_svc.size();
+  return 0;
+}
+
+// 2b. the batch takes the walk's layout; the ScopeSpans the host left are walked
+//     on the GPU (*redo: one needs the host walk).  *n: the spans, *S: the scopes.
+int walk_scopes(Engine* e, OtlpEngine* o, OtlpBatchImpl* b, const uint8_t* pb, size_t len, hipStream_t st,
+                bool gpu_scopes, bool gpu_res, Walked& w, OtlpResArgs* ra, uint64_t R, uint64_t* S, uint64_t* n,
+                bool* redo) {
   b->pb = pb;
   b->pb_len = len;
   b->lay = std::move(w.lay);
   b->layout_on_host = true;
   b->res_on_device = gpu_res;
-  ose_columns& c = b->cols;
-  c = ose_columns{};
-  c.n_resources = (uint32_t)R;
-  uint64_t n = 0;
+  b->cols = ose_columns{};
+  b->cols.n_resources = (uint32_t)R;
   b->scopes_dev = false;
   if (gpu_scopes) {
-    bool redo = false;
-    rc = scope_walk_gpu(e, b, w, st, &n, &redo, gpu_res ? &ra : nullptr, S);
+    int rc = scope_walk_gpu(e, b, w, st, n, redo, gpu_res ? ra : nullptr, *S);
     if (gpu_res) {   // (also before an error return or a redo: no copy into seth may stay in flight)
       const int src = res_sets_finish(o, b, w, st);
       if (!rc) rc = src;
     }
-    if (rc) return rc;
-    if (redo) {   // a scope needs the host walk: all on the host
-      b->walk_info[4] = 1;
-      return decode(e, pb, len, st, b, true, true);
-    }
+    if (rc || *redo) return rc;
     b->scopes_dev = true;
   } else {
-    n = w.span_ref.size();
+    *n = w.span_ref.size();
     b->span_ref = std::move(w.span_ref);
   }
-  if (!gpu_res) S = b->lay.scope_ref.size();
-  if (n > 0xFFFFFFF0ull) return fail(OSE_ERANGE, "OTLP ingest: more than 2^32-16 spans");
+  if (!gpu_res) *S = b->lay.scope_ref.size();
+  if (*n > 0xFFFFFFF0ull) return fail(OSE_ERANGE, "OTLP ingest: more than 2^32-16 spans");
+  return 0;
+}
+
+// 2c. the device columns, one slab: the walk's arrays that the GPU walks did
+//     not leave on the device go up through staging, the span kernels' outputs
+//     follow.  *span_ref_out: the spans' refs, *hl: the host-pass list (count zeroed).
+int column_slab(OtlpEngine* o, OtlpBatchImpl* b, Walked& w, const OtlpResArgs& ra, bool gpu_scopes, bool gpu_res,
+                bool sql, uint64_t n, uint64_t R, uint64_t S, hipStream_t st, uint64_t** span_ref_out, HostList* hl) {
+  ose_columns& c = b->cols;   // (scope_size / scope_resource are set by the GPU scope walk)
   const uint32_t K = o->n_attr_keys;
   b->attrsets = std::move(w.sets);
-  ProtoSizer sizer;
-  // device columns: one slab
   const uint64_t N = std::max<uint64_t>(n, 1);
-  struct Part { void** dst; size_t bytes; const void* src; };
-  uint8_t* host_flag = nullptr;
-  uint32_t* host_count = nullptr;
-  uint32_t* host_list = nullptr;
-  uint64_t* span_ref = nullptr;
-  const ose_columns keep_scope = c;   // scope_size / scope_resource set by the GPU walk
-  std::vector<Part> parts = {
+  uint64_t*& span_ref = *span_ref_out;
+  hl->cap = (uint32_t)N;
+  std::vector<SlabPart> parts = {
       {(void**)&span_ref, 8 * N, gpu_scopes ? nullptr : b->span_ref.data()},
       {(void**)&c.resource, 4 * N, gpu_scopes ? nullptr : w.span_res.data()},
       {(void**)&c.scope, 4 * N, gpu_scopes ? nullptr : w.span_scope.data()},
@@ -1569,46 +1254,27 @@ int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchIm
     parts.push_back({(void**)&c.scope_size, 4 * S, w.scope_size.data()});
     parts.push_back({(void**)&c.scope_resource, 4 * S, w.scope_res.data()});
   }
-  const std::vector<Part> outs = {
+  parts.insert(parts.end(), {
       // outputs of the decoder
-      {(void**)&c.trace_id, 16 * N, nullptr},
-      {(void**)&c.start_ns, 8 * N, nullptr},
-      {(void**)&c.end_ns, 8 * N, nullptr},
-      {(void**)&c.status, N, nullptr},
-      {(void**)&c.kind, N, nullptr},
-      {(void**)&c.url_flags, N, nullptr},
-      {(void**)&c.path, 8 * N, nullptr},
-      {(void**)&c.route, 8 * N, nullptr},
-      {(void**)&c.span_size, 4 * N, nullptr},
-      {(void**)&c.name_len, 4 * N, nullptr},
-      {(void**)&host_flag, N, nullptr},
-      {(void**)&host_count, 16, nullptr},
-      {(void**)&host_list, 4 * N, nullptr},
-  };
-  parts.insert(parts.end(), outs.begin(), outs.end());
-  if (o->json_rules) parts.push_back({(void**)&c.attr_match, 8 * N * (size_t)o->attr_words, nullptr});
+      {(void**)&c.trace_id, 16 * N}, {(void**)&c.start_ns, 8 * N}, {(void**)&c.end_ns, 8 * N},
+      {(void**)&c.status, N}, {(void**)&c.kind, N}, {(void**)&c.url_flags, N},
+      {(void**)&c.path, 8 * N}, {(void**)&c.route, 8 * N}, {(void**)&c.span_size, 4 * N},
+      {(void**)&c.name_len, 4 * N},
+      {(void**)&hl->flag, N}, {(void**)&hl->count, 16}, {(void**)&hl->list, 4 * N},
+  });
+  if (o->json_rules) parts.push_back({(void**)&c.attr_match, 8 * N * (size_t)o->attr_words});
   if (sql) {
-    parts.push_back({(void**)&c.db_flags, N, nullptr});
-    parts.push_back({(void**)&c.db_query, 8 * N, nullptr});
+    parts.push_back({(void**)&c.db_flags, N});
+    parts.push_back({(void**)&c.db_query, 8 * N});
   }
   if (K) {
-    parts.push_back({(void**)&c.attr_type, (size_t)K * N, nullptr});
-    parts.push_back({(void**)&c.attr_val, 8 * (size_t)K * N, nullptr});
+    parts.push_back({(void**)&c.attr_type, (size_t)K * N});
+    parts.push_back({(void**)&c.attr_val, 8 * (size_t)K * N});
   }
-  size_t total = 0, inputs = 0;
-  for (auto& p : parts) {
-    total = up(total + p.bytes + 16);
-    if (p.src) inputs = total;
-  }
-  if ((rc = b->slab.need(total)) || (rc = b->stage.need(inputs))) return rc;
-  size_t off = 0;
-  for (auto& p : parts) {
-    *p.dst = b->slab.p + off;
-    if (p.src && p.bytes) std::memcpy(b->stage.p + off, p.src, p.bytes);
-    off = up(off + p.bytes + 16);
-  }
-  if (inputs) HIP_TRY(hipMemcpyAsync(b->slab.p, b->stage.p, inputs, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemsetAsync(host_count, 0, 16, st));
+  SlabSize z;
+  if (int rc = slab_place(b->slab, parts, &b->stage, &z)) return rc;
+  if (z.inputs) HIP_TRY(hipMemcpyAsync(b->slab.p, b->stage.p, z.inputs, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(hl->count, 0, 16, st));
   if (gpu_res) {   // the resource columns the GPU pass wrote
     c.res_svc = ra.res_svc;
     c.res_svc_str = ra.res_svc_str;
@@ -1618,8 +1284,6 @@ int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchIm
     c.res_sql_ok = ra.res_sql_ok;
   }
   if (gpu_scopes) {
-    c.scope_size = keep_scope.scope_size;
-    c.scope_resource = keep_scope.scope_resource;
     // pass 2: the span refs of every scope at their place
     OtlpScopeArgs sa = b->sargs;
     sa.span_ref = span_ref;
@@ -1633,17 +1297,21 @@ int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchIm
   }
   b->d_spans = span_ref;
   c.n_spans = n;
-  c.n_resources = (uint32_t)R;
-  c.n_scopes = (uint32_t)S;
+  c.n_scopes = (uint32_t)S;   // (n_resources: walk_scopes)
   c.n_attrsets = (uint32_t)b->attrsets.size();
   c.arena = b->arena.p;
-  c.arena_bytes = len;
+  c.arena_bytes = b->pb_len;
   c.n_attr_keys = K;
   c.attr_match_words = o->attr_words;
   if (!o->ctx.url_filter) c.res_url_ok = nullptr;
-  std::vector<uint64_t>& attr_res = w.attr_res;
-  lap(2);
-  // 3. the GPU decoder
+  return 0;
+}
+
+// 3. the GPU decoder: otlp_span_kernel, then (sql) otlp_sqlop_kernel and (ca)
+//    otlp_condattr_kernel; *cnt: the spans on the host-pass list once they have run
+int span_kernels(Engine* e, OtlpEngine* o, OtlpBatchImpl* b, uint64_t n, const uint64_t* span_ref, const HostList& hl,
+                 bool sql, bool ca, hipStream_t st, uint32_t* cnt) {
+  const ose_columns& c = b->cols;
   OtlpArgs a{};
   a.pb = b->arena.p;
   a.n_spans = n;
@@ -1651,26 +1319,11 @@ int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchIm
   a.keys = reinterpret_cast<const OtlpKeyDev*>(o->keys_dev);
   a.key_bytes = o->keys_dev + o->keys.size() * sizeof(OtlpKeyDev);
   a.n_keys = (uint32_t)o->keys.size();
-  a.n_attr_keys = K;
+  a.n_attr_keys = o->n_attr_keys;
   a.attr_words = o->attr_words;
   a.key_lens = o->key_lens;
-  a.tid = const_cast<uint64_t*>(c.trace_id);
-  a.start = const_cast<uint64_t*>(c.start_ns);
-  a.end = const_cast<uint64_t*>(c.end_ns);
-  a.status = const_cast<uint8_t*>(c.status);
-  a.kind = const_cast<uint8_t*>(c.kind);
-  a.url_flags = const_cast<uint8_t*>(c.url_flags);
-  a.path = const_cast<ose_strref*>(c.path);
-  a.route = const_cast<ose_strref*>(c.route);
-  a.span_size = const_cast<uint32_t*>(c.span_size);
-  a.name_len = const_cast<uint32_t*>(c.name_len);
-  a.attr_match = const_cast<uint64_t*>(c.attr_match);
-  a.attr_type = const_cast<uint8_t*>(c.attr_type);
-  a.attr_val = const_cast<uint64_t*>(c.attr_val);
-  a.host_flag = host_flag;
-  a.host_count = host_count;
-  a.host_list = host_list;
-  a.host_cap = (uint32_t)N;
+  set_span_columns(a, c);
+  set_host_list(a, hl);
   (void)hipGetLastError();   // a stale error of an earlier call must not be reported as this launch's
   Engine::Timed tm{};
   e->prof_begin("otlp_span_kernel", st, tm);
@@ -1684,24 +1337,31 @@ int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchIm
     qa.span_ref = span_ref;
     qa.db_flags = const_cast<uint8_t*>(c.db_flags);
     qa.db_query = const_cast<ose_strref*>(c.db_query);
-    qa.host_flag = host_flag;
-    qa.host_count = host_count;
-    qa.host_list = host_list;
-    qa.host_cap = (uint32_t)N;
+    set_host_list(qa, hl);
     Engine::Timed tq{};
     e->prof_begin("otlp_sqlop_kernel", st, tq);
     launch_otlp_sqlop(qa, st);
     HIP_TRY(hipGetLastError());
     e->prof_end(tq, st);
   }
-  if (ca && (rc = condattr_spans(e, b, n, span_ref, host_flag, host_count, host_list, st))) return rc;
-  // 4. the host pass
-  uint32_t cnt = 0;
-  HIP_TRY(hipMemcpyAsync(&cnt, host_count, 4, hipMemcpyDeviceToHost, st));
+  if (ca)
+    if (int rc = condattr_spans(e, b, n, span_ref, hl, st)) return rc;
+  *cnt = 0;
+  HIP_TRY(hipMemcpyAsync(cnt, hl.count, 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
-  b->host_spans = cnt;
-  lap(3);
-  if (!cnt) return ca ? condattr_finish(e, b, pb, {}, host_list, st) : 0;
+  b->host_spans = *cnt;
+  return 0;
+}
+
+// 4. the host pass over the `cnt` listed spans (list: their indices, fetched
+//    here): the records and the strings go up through staging
+int host_pass(OtlpEngine* o, OtlpBatchImpl* b, const uint8_t* pb, Walked& w, bool gpu_res, bool sql, uint32_t cnt,
+              const uint32_t* host_list, hipStream_t st, std::vector<uint32_t>& list) {
+  int rc;
+  ose_columns& c = b->cols;
+  const uint64_t n = c.n_spans, R = c.n_resources;
+  const uint32_t K = o->n_attr_keys;
+  std::vector<uint64_t>& attr_res = w.attr_res;
   std::vector<uint32_t> span_res;
   const std::vector<uint32_t>* sres = &w.span_res;
   if (gpu_res && !o->wide_host_rules) {   // the resources' span_attribute service bits from the device
@@ -1723,7 +1383,7 @@ int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchIm
     HIP_TRY(hipMemcpy(span_res.data(), b->d_span_res, 4 * n, hipMemcpyDeviceToHost));
     sres = &span_res;
   }
-  std::vector<uint32_t> list(cnt);
+  list.resize(cnt);
   HIP_TRY(hipMemcpy(list.data(), host_list, 4 * (size_t)cnt, hipMemcpyDeviceToHost));
   std::vector<OtlpFix> fix(cnt);
   std::vector<uint8_t> fix_type((size_t)cnt * K);
@@ -1731,14 +1391,15 @@ int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchIm
   const uint32_t AW = o->json_rules ? o->attr_words : 0;   // attr_match words the host pass writes per span
   std::vector<uint64_t> fix_attr((size_t)cnt * AW);
   std::vector<OtlpSqlFix> fix_sql(sql ? cnt : 0);   // db_flags / db_query (AsString included) of the listed spans
-  std::string strs;   // appended after the message bytes
-  const size_t str_base = pb_cap;
+  std::string strs;   // appended after the message bytes and their zero slack
+  const size_t str_base = up(b->pb_len + 16, 16);
   auto put = [&](std::string_view s) {
     ose_strref r{(uint32_t)(str_base + strs.size()), (uint32_t)s.size()};
     strs += s;
     return r;
   };
   SpanCols sc;
+  ProtoSizer sizer;
   std::vector<uint64_t> res_words;
   for (uint32_t q = 0; q < cnt; q++) {
     const uint32_t i = list[q];
@@ -1780,24 +1441,15 @@ int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchIm
     if (sql)
       fix_sql[q] = OtlpSqlFix{i, sc.db_flags, (sc.db_flags & OSE_DB_HAS_QUERY) ? put(sc.db_query) : ose_strref{0, 0}};
   }
-  if (str_base + strs.size() + 16 > b->arena.cap) {
-    // a larger arena: the message bytes move with it
-    DevBuf bigger;
-    if ((rc = bigger.need(str_base + strs.size() + 16))) return rc;
-    HIP_TRY(hipMemcpyAsync(bigger.p, b->arena.p, pb_cap, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    std::swap(b->arena.p, bigger.p);
-    std::swap(b->arena.cap, bigger.cap);
-    c.arena = b->arena.p;
-    b->walk_info[7] = 1;
-  }
+  if ((rc = regrow_arena(b, str_base, str_base + strs.size() + 16, st))) return rc;   // the message bytes move with it
   c.arena_bytes = str_base + strs.size();
+  // the records' layout, the same in staging and on the device (plain sums:
+  // the OtlpFix part has no 16-byte slack, so the slab carver's rule is not it)
   const size_t fb = up(cnt * sizeof(OtlpFix)), tb = up((size_t)cnt * K + 16), vb = up((size_t)cnt * K * 8 + 16);
   const size_t ab = up((size_t)cnt * AW * 8 + 16), qb = up(fix_sql.size() * sizeof(OtlpSqlFix) + 16);
   const size_t fixb = fb + tb + vb + ab + qb;
-  if ((rc = b->stage.need(fixb + strs.size() + 16))) return rc;
   DevBuf& fixdev = b->fixdev;
-  if ((rc = fixdev.need(fixb))) return rc;
+  if ((rc = b->stage.need(fixb + strs.size() + 16)) || (rc = fixdev.need(fixb))) return rc;
   std::memcpy(b->stage.p, fix.data(), cnt * sizeof(OtlpFix));
   if (K) {
     std::memcpy(b->stage.p + fb, fix_type.data(), (size_t)cnt * K);
@@ -1818,19 +1470,7 @@ int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchIm
   fa.fix = reinterpret_cast<const OtlpFix*>(fixdev.p);
   fa.fix_type = fixdev.p + fb;
   fa.fix_val = reinterpret_cast<const uint64_t*>(fixdev.p + fb + tb);
-  fa.tid = a.tid;
-  fa.start = a.start;
-  fa.end = a.end;
-  fa.status = a.status;
-  fa.kind = a.kind;
-  fa.url_flags = a.url_flags;
-  fa.path = a.path;
-  fa.route = a.route;
-  fa.span_size = a.span_size;
-  fa.name_len = a.name_len;
-  fa.attr_match = a.attr_match;
-  fa.attr_type = a.attr_type;
-  fa.attr_val = a.attr_val;
+  set_span_columns(fa, c);
   launch_otlp_fix(fa, st);
   HIP_TRY(hipGetLastError());
   if (sql) {
@@ -1839,8 +1479,64 @@ int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchIm
     HIP_TRY(hipGetLastError());
   }
   HIP_TRY(hipStreamSynchronize(st));   // fixdev and the staging are reused / freed
-  if (ca && (rc = condattr_finish(e, b, pb, list, host_list, st))) return rc;
-  lap(4);
+  return 0;
+}
+
+int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchImpl* b, bool host_scopes = false,
+           bool host_res = false) {
+  int rc;
+  OtlpEngine* o = otlp_engine(e, rc);
+  if (!o) return rc;
+  if (len > 0xFFFFFFF0ull) return fail(OSE_ERANGE, "OTLP ingest: message beyond the 4 GiB arena range");
+  using clk = std::chrono::steady_clock;
+  auto t0 = clk::now();
+  auto lap = [&](int k) {
+    const auto t = clk::now();
+    b->t_ms[k] = std::chrono::duration<double, std::milli>(t - t0).count();
+    t0 = t;
+  };
+  for (double& x : b->t_ms) x = 0;
+  for (int k = 0; k < 8; k++)
+    if (k != 4 && k != 5) b->walk_info[k] = 0;   // (the redo flags are the outer call's)
+  // engine option otlp_sqlop: db_flags / db_query / res_sql_ok are decoded too
+  const bool sql = e->has_sqlop && e->option(Engine::kOptOtlpSqlop);
+  // engine option otlp_condattr: odigosconditionalattributes' columns are decoded too
+  const bool ca = e->has_condattr && e->option(Engine::kOptOtlpCondattr);
+  b->ca_on = false;
+  // the walk: TracesData and ResourceSpans on the host, ScopeSpans up to
+  // 64 KB on the GPU (engine option otlp_host_scopes: all on the host)
+  // (otlp_host_resources: ResourceSpans on the host, ScopeSpans on the
+  // GPU; without it only the TracesData chain is walked on the host)
+  const bool gpu_scopes = !host_scopes && !e->option(Engine::kOptOtlpHostScopes);
+  const bool gpu_res = gpu_scopes && !host_res && !e->option(Engine::kOptOtlpHostResources);
+  bool pinned = false, redo = false;
+  if ((rc = upload_message(b, pb, len, st, &pinned))) return rc;
+  lap(0);
+  Walked w;
+  OtlpResArgs ra{};
+  uint64_t R = 0, S = 0, n = 0;
+  if ((rc = walk_records(o, b, pb, len, st, gpu_scopes, gpu_res, !pinned, sql, w, &ra, &R, &S, &redo))) return rc;
+  if (redo) {   // a malformed record: the host walk reports it
+    b->walk_info[5] = 1;
+    return decode(e, pb, len, st, b, false, true);
+  }
+  lap(1);
+  if ((rc = walk_scopes(e, o, b, pb, len, st, gpu_scopes, gpu_res, w, &ra, R, &S, &n, &redo))) return rc;
+  if (redo) {   // a scope needs the host walk: all on the host
+    b->walk_info[4] = 1;
+    return decode(e, pb, len, st, b, true, true);
+  }
+  uint64_t* span_ref = nullptr;
+  HostList hl;
+  if ((rc = column_slab(o, b, w, ra, gpu_scopes, gpu_res, sql, n, R, S, st, &span_ref, &hl))) return rc;
+  lap(2);
+  uint32_t cnt = 0;
+  if ((rc = span_kernels(e, o, b, n, span_ref, hl, sql, ca, st, &cnt))) return rc;
+  lap(3);
+  std::vector<uint32_t> list;   // the host pass's spans: none without a count
+  if (cnt && (rc = host_pass(o, b, pb, w, gpu_res, sql, cnt, hl.list, st, list))) return rc;
+  if (ca && (rc = condattr_finish(e, b, pb, list, hl.list, st))) return rc;
+  if (cnt) lap(4);
   return 0;
 }
 }  // namespace
