@@ -357,8 +357,18 @@ typedef struct ose_batch ose_batch;
  * table: a chunk of its own, its bytes past the LDS copy read from HBM);
  * more than about 500 distinct service names among the rules: each chunk
  * indexes its own rules' services (ose_shard_pack / ose_shard_decide then
- * return OSE_ENOTSUP).  OSE_ENOTSUP remains for regexps whose DFA exceeds
- * about two million states (or 256 MiB of transitions).                     */
+ * return OSE_ENOTSUP).  An odigosurltemplate regexp (custom_ids, {name:re}
+ * and regex: rule segments) whose DFA exceeds about two million states or
+ * 256 MiB of transitions, or needs more than 255 rune classes, is held as an
+ * NFA program instead and matched on the GPU by a bit-set simulation, linear
+ * in pattern x input; every TEMPLATE call of such an engine plans and writes
+ * all its spans per lane (the wave-parallel planner has no NFA matcher).
+ * Finding out costs the subset construction up to its cap, about 5 s per
+ * such regexp, at engine creation only (the class-count case costs nothing).
+ * OSE_ENOTSUP remains past the NFA bound: a regexp of more than 100,000
+ * instructions or whose NFA tables exceed 256 MiB (^(?:a|b)*a(?:a|b){1000}$,
+ * Go's largest repeat count, takes about 100 KB), and for span_attribute
+ * regexps evaluated on the GPU whose DFA exceeds the bounds above.           */
 int ose_engine_create(const char* cfg_json, ose_engine** out);
 /* The engine's batches (ose_batch, ose_otlp_batch, ose_otlp_out, ose_gbt)
  * may be released before or after this call: each holds a reference, and
@@ -408,6 +418,10 @@ uint32_t ose_engine_attr_host_rules(const ose_engine* eng, uint64_t* words, uint
  * Synchronises the engine's device.  Writes min(cap, 5) counters and
  * returns 5.                                                                */
 uint32_t ose_engine_path_counts(ose_engine* eng, uint64_t* counts, uint32_t cap);
+/* With "url_path_counts" on: the 64-span groups of the engine's most recent
+ * TEMPLATE call that took the NFA route (every group when the URL tables hold
+ * an NFA program, 0 otherwise).  Synchronises the engine's device.           */
+uint64_t ose_engine_url_nfa_groups(ose_engine* eng);
 
 /* Attribute key k (< n_attr_keys) of the attr_type / attr_val columns; the
  * bytes stay valid for the engine's lifetime.                               */
@@ -444,7 +458,16 @@ int ose_engine_attr_key(const ose_engine* eng, uint32_t k, const char** key, uin
  *   "url_path_counts"      every TEMPLATE call queues two 4-byte device copies
  *                          behind url_emit_slow_kernel, which keep the call's
  *                          list lengths for ose_engine_path_counts (counts[3],
- *                          counts[4]).  Off by default: nothing extra is queued.
+ *                          counts[4]) and ose_engine_url_nfa_groups.  Off by
+ *                          default: nothing extra is queued.
+ * and one test and measurement seam:
+ *   "url_regex_nfa"        the odigosurltemplate tables are built again with
+ *                          every user regexp as an NFA program and TEMPLATE
+ *                          takes the NFA route, so a config whose regexps
+ *                          have DFAs runs both routes on the same batch; off
+ *                          again goes back to the tables of ose_engine_create.
+ *                          Set between calls, not during one.  OSE_EINVAL on
+ *                          an engine without the odigosurltemplate section.
  * OSE_EINVAL for any other name.                                            */
 int ose_engine_set_option(ose_engine* eng, const char* name, int64_t value);
 

@@ -290,7 +290,9 @@ class Engine:
         native.check(self.L.ose_profile_enable(self.h, int(on)))
 
     def set_option(self, name: str, value: int = 1):
-        """ose_engine_set_option: the alternative OTLP legs (tests).  Once
+        """ose_engine_set_option: the alternative OTLP legs (tests), and
+        "url_regex_nfa": every odigosurltemplate regexp as an NFA program
+        (set between calls).  Once
         "url_path_counts" has been turned on, path_counts() keeps its two URL
         keys for this engine, also after the option is turned off again."""
         native.check(self.L.ose_engine_set_option(self.h, name.encode(), int(value)))
@@ -301,12 +303,13 @@ class Engine:
         """ose_engine_path_counts: how often SAMPLE left its fast path; once
         the option "url_path_counts" has been set on this engine, also the
         groups of the last TEMPLATE call that url_plan_slow_kernel planned
-        (url_unplanned) and url_emit_slow_kernel emitted (url_slow)."""
+        (url_unplanned) and url_emit_slow_kernel emitted (url_slow), and the
+        groups that took the NFA route (url_nfa)."""
         c = (C.c_uint64 * 5)()
         self.L.ose_engine_path_counts(self.h, c, 5)
         out = {"run_list": int(c[0]), "sort": int(c[1]), "long_runs": int(c[2])}
         if getattr(self, "_url_counts", False):
-            out.update(url_unplanned=int(c[3]), url_slow=int(c[4]))
+            out.update(url_unplanned=int(c[3]), url_slow=int(c[4]), url_nfa=int(self.L.ose_engine_url_nfa_groups(self.h)))
         return out
 
     def profile_read(self) -> dict:

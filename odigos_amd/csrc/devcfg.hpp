@@ -17,19 +17,41 @@ struct DfaDev {
   uint8_t ascii[128];   // class of runes 0..127
 };
 
+// One regexp as an NFA program (regex_nfa.hpp, regex_nfa_device.hpp): the
+// route of a regexp whose DFA passes the bounds above.  M rune instructions;
+// entry j < M is "rune instruction j taken", entry M the start instruction.
+// Offsets are byte offsets from this header (the program is one relocatable
+// image), 16-byte aligned.
+struct NfaDev {
+  uint32_t m;             // rune instructions
+  uint32_t words;         // (m + 31) / 32, >= 1: words of one state bit set
+  uint32_t nclasses;      // rune classes (16-bit ids)
+  uint32_t nctx;          // distinct EmptyOpContext tables, <= 16
+  uint32_t hi_n;          // number of non-ASCII ranges
+  uint32_t hi_off;        // uint32 triplets {lo, hi, cls}
+  uint32_t row_off;       // uint32 [nctx][m + 2]: CSR rows of succ, one per entry
+  uint32_t succ_off;      // uint32 []: the rune instructions an entry's epsilon closure reaches
+  uint32_t match_off;     // uint32 [nctx][(m + 32) / 32]: bit j: entry j's closure holds MATCH
+  uint32_t in_class_off;  // uint32 [nclasses][words]: bit j: rune instruction j's set holds the class
+  uint32_t cls_type_off;  // uint8 [nclasses]: EmptyOpContext type of the class
+  uint32_t total_bytes;   // of the image
+  uint8_t ctx_of[16];     // context table of [previous type * 4 + next type]
+  uint16_t ascii[128];    // class of runes 0..127
+};
+
 // odigosurltemplate tables.
 enum : uint32_t { kRuleStatic = 0, kRuleWildcard = 1, kRuleTemplate = 2, kRuleRegex = 3 };
 struct UrlRuleSegDev {
   uint32_t kind;
   uint32_t text_off, text_len;   // static text or template name (in bytes section)
-  int32_t dfa;                   // index into dfa table, -1 = none
+  int32_t dfa;                   // index into dfa table, -1 = none; <= -2: NFA program -2 - dfa (nfa_off table)
 };
 struct UrlRuleDev {
   uint32_t nseg;
   uint32_t seg_first;            // index into rule segment table
 };
 struct UrlCustomDev {
-  int32_t dfa;
+  int32_t dfa;                   // as UrlRuleSegDev::dfa (never -1)
   uint32_t name;                 // index into name table
 };
 struct NameDev {
@@ -51,7 +73,10 @@ struct UrlCfgDev {
   uint32_t dfa_off;              // uint32 [n_dfa] byte offsets of DfaDev
   uint32_t bytes_off;            // raw text bytes
   uint32_t total_bytes;
+  uint32_t n_nfa;                // regexps held as NFA programs (the engine then takes the per-lane route)
+  uint32_t nfa_off;              // uint32 [n_nfa] byte offsets of NfaDev images; 0 when n_nfa is 0
 };
+inline int32_t url_nfa_code(uint32_t k) { return -2 - (int32_t)k; }
 
 }  // namespace ose
 

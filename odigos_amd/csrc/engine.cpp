@@ -19,6 +19,7 @@
 #include "kernels.hpp"
 #include "blob.hpp"
 #include "regex_dfa.hpp"
+#include "regex_nfa.hpp"
 
 namespace ose {
 
@@ -32,7 +33,14 @@ int fail(int code, const std::string& msg) {
 // odigosurltemplate tables: newUrlTemplateProcessor (processor.go:27-69)
 // groups rules by segment count keeping config order; custom ids default
 // their name to "id".
-int build_url_blob(const UrlTemplateConfig& c, std::vector<uint8_t>& out, uint32_t& max_name) {
+// A regexp goes to the DFA compiler first, with its caps; only TooLarge (the
+// state or table cap after the subset construction ran into it, seconds per
+// such regexp; or more than 255 rune classes, at once) sends it to the NFA
+// compiler (regex_nfa.hpp), so a regexp with a DFA keeps its table.
+// force_nfa (engine option url_regex_nfa): every regexp as an NFA program.
+// nfa_words: the widest program's state words (0: the tables hold no NFA).
+int build_url_blob(const UrlTemplateConfig& c, std::vector<uint8_t>& out, uint32_t& max_name, bool force_nfa,
+                   uint32_t& nfa_words) {
   Blob bl;
   UrlCfgDev h{};
   bl.put(&h, 1);
@@ -47,15 +55,30 @@ int build_url_blob(const UrlTemplateConfig& c, std::vector<uint8_t>& out, uint32
   names.push_back(add_text("date"));
   names.push_back(add_text("email"));
   std::vector<Dfa> dfas;
+  std::vector<std::vector<uint8_t>> nfas;
+  nfa_words = 0;
   auto compile = [&](const std::string& rx, int32_t& idx) -> int {
     Dfa d;
     std::string err;
-    RegexStatus st = compile_dfa(rx, d, err);
+    RegexStatus st = force_nfa ? RegexStatus::TooLarge : compile_dfa(rx, d, err);
+    if (st == RegexStatus::Ok) {
+      idx = (int32_t)dfas.size();
+      dfas.push_back(std::move(d));
+      return 0;
+    }
+    if (st == RegexStatus::TooLarge) {
+      NfaProgram np;
+      err.clear();
+      st = compile_nfa(rx, np, err);
+      if (st == RegexStatus::Ok) {
+        idx = url_nfa_code((uint32_t)nfas.size());
+        nfa_words = std::max(nfa_words, np.words());
+        nfas.push_back(nfa_image(np));
+        return 0;
+      }
+    }
     if (st == RegexStatus::Syntax) return fail(OSE_EINVAL, err);
-    if (st != RegexStatus::Ok) return fail(OSE_ENOTSUP, "regexp not supported by the DFA compiler: " + err);
-    idx = (int32_t)dfas.size();
-    dfas.push_back(std::move(d));
-    return 0;
+    return fail(OSE_ENOTSUP, "regexp not supported by the DFA and NFA compilers: " + err);
   };
   std::vector<UrlCustomDev> custom;
   for (auto& ci : c.custom_ids) {
@@ -129,8 +152,17 @@ int build_url_blob(const UrlTemplateConfig& c, std::vector<uint8_t>& out, uint32
   for (auto& d : dfas) dfa_offs.push_back(put_dfa(bl, d));
   h.dfa_off = bl.put(dfa_offs.data(), dfa_offs.size());
   h.bytes_off = bl.put(bytes.data(), bytes.size());
+  // the NFA programs go behind everything a config without one has, so its
+  // tables are where they always were
+  if (!nfas.empty()) {
+    std::vector<uint32_t> nfa_offs;
+    for (auto& im : nfas) nfa_offs.push_back(bl.put(im.data(), im.size()));
+    h.n_nfa = (uint32_t)nfas.size();
+    h.nfa_off = bl.put(nfa_offs.data(), nfa_offs.size());
+  }
   bl.align();
-  if (bl.overflow) return fail(OSE_ENOTSUP, "odigosurltemplate device tables exceed 4 GiB (the regexps' DFAs together)");
+  if (bl.overflow)
+    return fail(OSE_ENOTSUP, "odigosurltemplate device tables exceed 4 GiB (the regexps' DFAs and NFA programs together)");
   bl.b.resize(bl.b.size() + 16, 0);
   h.total_bytes = (uint32_t)bl.b.size();
   std::memcpy(bl.b.data(), &h, sizeof h);
@@ -149,6 +181,7 @@ Engine::~Engine() {
   for (auto s : streams) (void)hipStreamDestroy(s);
   for (auto ev : event_pool) (void)hipEventDestroy(ev);
   if (url_blob_dev) (void)hipFree(url_blob_dev);
+  if (url_blob_forced_dev) (void)hipFree(url_blob_forced_dev);
   for (auto* d : sampling_chunks_dev)
     if (d) (void)hipFree(d);   // (sampling_blob_dev is the first)
   for (auto* d : sampling_svc_map_dev)
@@ -381,8 +414,11 @@ int run_url(Engine* e, const ose_columns* c, const ose_outputs* o, hipStream_t s
   const size_t off_dbg = align_up(off_unpl + 4 * (size_t)groups, 256);
   const size_t off_scr = off_dbg + 256;
   const size_t scr_bytes = url_scratch_bytes(n, c->arena_bytes);
-  const size_t need = off_scr + (refs ? 0 : scr_bytes);   // refs: the images go to tmpl_arena itself
-  if (need > url_workspace_bytes(n, c->arena_bytes))
+  // refs: the images go to tmpl_arena itself; an NFA engine's state slab follows
+  const uint32_t nfa_words = e->url_words();
+  const size_t off_slab = align_up(off_scr + (refs ? 0 : scr_bytes), 256);
+  const size_t need = nfa_words ? off_slab + url_nfa_slab_bytes(n, nfa_words) - 256 : off_scr + (refs ? 0 : scr_bytes);
+  if (need > url_workspace_bytes(n, c->arena_bytes, nfa_words))
     return fail(OSE_EINVAL, "internal: URL workspace layout exceeds its bound");
   int rc = ws->reserve(ws_off + need);
   if (rc) return rc;
@@ -400,7 +436,10 @@ int run_url(Engine* e, const ose_columns* c, const ose_outputs* o, hipStream_t s
   a.tmpl = o->tmpl;
   a.out_arena = o->tmpl_arena;
   a.out_cap = o->tmpl_arena_cap;
-  a.cfg = e->url_blob_dev;
+  a.cfg = e->url_forced() ? e->url_blob_forced_dev : e->url_blob_dev;
+  a.nfa = nfa_words ? 1u : 0u;
+  a.nfa_words = nfa_words;
+  a.nfa_slab = nfa_words ? reinterpret_cast<uint32_t*>(base + off_slab) : nullptr;
   a.general = (!e->url.custom_ids.empty() || !e->url.templatization_rules.empty()) ? 1u : 0u;
   a.plan_len = reinterpret_cast<uint32_t*>(base + off_len);
   a.plan_meta = reinterpret_cast<uint32_t*>(base + off_meta);
@@ -446,14 +485,25 @@ int run_url(Engine* e, const ose_columns* c, const ose_outputs* o, hipStream_t s
     HIP_TRY(hipMemsetAsync(a.dbg, 0, 256, st));
   }
   Engine::Timed tm{};
-  e->prof_begin("url_plan_kernel", st, tm);
-  launch_url_plan(a, st);
-  HIP_TRY(hipGetLastError());
-  e->prof_end(tm, st);
-  e->prof_begin("url_plan_slow_kernel", st, tm);
-  launch_url_plan_slow(a, st);
-  HIP_TRY(hipGetLastError());
-  e->prof_end(tm, st);
+  if (a.nfa) {   // every group listed as unplanned, then planned per lane
+    e->prof_begin("url_nfa_fill_kernel", st, tm);
+    launch_url_nfa_fill(a, st);
+    HIP_TRY(hipGetLastError());
+    e->prof_end(tm, st);
+    e->prof_begin("url_nfa_plan_kernel", st, tm);
+    launch_url_nfa_plan(a, st);
+    HIP_TRY(hipGetLastError());
+    e->prof_end(tm, st);
+  } else {
+    e->prof_begin("url_plan_kernel", st, tm);
+    launch_url_plan(a, st);
+    HIP_TRY(hipGetLastError());
+    e->prof_end(tm, st);
+    e->prof_begin("url_plan_slow_kernel", st, tm);
+    launch_url_plan_slow(a, st);
+    HIP_TRY(hipGetLastError());
+    e->prof_end(tm, st);
+  }
   if (planned) HIP_TRY(hipEventRecord(planned, st));
   e->prof_begin("url_scan_kernel", st, tm);
   launch_url_scan(a, st);
@@ -463,8 +513,9 @@ int run_url(Engine* e, const ose_columns* c, const ose_outputs* o, hipStream_t s
   // bases: nothing here reads SAMPLE's keep bytes or url_copy_kernel's
   // output, so it runs with the front (beside the trace stage when the
   // URL front has its own stream)
-  e->prof_begin("url_emit_slow_kernel", st, tm);
-  launch_url_emit_slow(a, st);
+  e->prof_begin(a.nfa ? "url_nfa_emit_kernel" : "url_emit_slow_kernel", st, tm);
+  if (a.nfa) launch_url_nfa_emit(a, st);
+  else launch_url_emit_slow(a, st);
   HIP_TRY(hipGetLastError());
   e->prof_end(tm, st);
   // "url_path_counts" (tests): which kernel took this call's groups, kept in
@@ -472,6 +523,9 @@ int run_url(Engine* e, const ose_columns* c, const ose_outputs* o, hipStream_t s
   if ((e->options.load() & Engine::kOptUrlPathCounts) && e->path_count_dev) {
     HIP_TRY(hipMemcpyAsync(e->path_count_dev + 2, a.unplanned_count, 4, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(e->path_count_dev + 3, a.slow_count, 4, hipMemcpyDeviceToDevice, st));
+    // word 4: the groups the NFA route took (ose_engine_url_nfa_groups)
+    if (a.nfa) HIP_TRY(hipMemcpyAsync(e->path_count_dev + 4, a.unplanned_count, 4, hipMemcpyDeviceToDevice, st));
+    else HIP_TRY(hipMemsetAsync(e->path_count_dev + 4, 0, 8, st));
   }
   if (front) {
     *front = a;
@@ -577,8 +631,8 @@ int run_stages(Engine* e, const ose_columns* c, const ose_outputs* o, uint32_t m
   const size_t url_off = (mask & OSE_STAGE_SAMPLE) ? align_up(defer ? sampling_scratch_bytes(n) : 256, 256) : 0;
   size_t size_off = (mask & OSE_STAGE_SAMPLE) ? 256 : 0;
   if (mask & OSE_STAGE_TEMPLATE) {
-    need = std::max(need, url_off + url_workspace_bytes(n, c->arena_bytes));
-    size_off = align_up(url_off + url_workspace_bytes(n, c->arena_bytes), 256);
+    need = std::max(need, url_off + url_workspace_bytes(n, c->arena_bytes, e->url_words()));
+    size_off = align_up(url_off + url_workspace_bytes(n, c->arena_bytes, e->url_words()), 256);
   }
   if (mask & OSE_STAGE_SIZE) need = std::max(need, size_off + size_scratch_bytes(c->n_scopes, c->n_resources));
   int rc = ws->reserve(need);
@@ -778,7 +832,7 @@ int ose_engine_create(const char* cfg_json, ose_engine** out) {
     e->has_condattr = true;
   }
   if (e->has_url) {
-    int rc = build_url_blob(e->url, e->url_blob_host, e->max_name);
+    int rc = build_url_blob(e->url, e->url_blob_host, e->max_name, false, e->url_nfa_words);
     if (rc) { delete e; return rc; }
   }
   int rc = e->build_sampling_tables();
@@ -900,6 +954,45 @@ uint32_t ose_engine_path_counts(ose_engine* eng, uint64_t* counts, uint32_t cap)
   return 5;
 }
 
+uint64_t ose_engine_url_nfa_groups(ose_engine* eng) {
+  if (!eng) return 0;
+  Engine* e = reinterpret_cast<Engine*>(eng);
+  uint64_t c = 0;
+  if (e->path_count_dev && bind_device(e) == 0) {
+    LastErrorScope keep("ose_engine_url_nfa_groups");
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(&c, e->path_count_dev + 4, 8, hipMemcpyDeviceToHost) != hipSuccess)
+      c = 0;
+  }
+  return c;
+}
+
+// FNV-1a of the odigosurltemplate device tables of an engine config, their
+// size and the number of NFA programs in them, for tests that pin the tables
+// of a config without an NFA program.  No device is touched.
+extern "C" int osehost_url_blob_hash(const char* cfg_json, int force_nfa, uint64_t* hash, uint64_t* bytes,
+                                     uint32_t* n_nfa) {
+  Json root;
+  try {
+    root = parse_json(cfg_json ? cfg_json : "{}");
+  } catch (const std::exception& ex) {
+    return fail(OSE_EINVAL, ex.what());
+  }
+  const Json* j = root.is_obj() ? root.get("odigosurltemplate") : nullptr;
+  if (!j) return fail(OSE_EINVAL, "odigosurltemplate is not configured");
+  UrlTemplateConfig url;
+  const std::string err = decode_url_config(*j, url);
+  if (!err.empty()) return fail(OSE_EINVAL, err);
+  std::vector<uint8_t> blob;
+  uint32_t max_name = 0, words = 0;
+  if (const int rc = build_url_blob(url, blob, max_name, force_nfa != 0, words)) return rc;
+  uint64_t h = 0xcbf29ce484222325ull;
+  for (uint8_t b : blob) h = (h ^ b) * 0x100000001b3ull;
+  if (hash) *hash = h;
+  if (bytes) *bytes = blob.size();
+  if (n_nfa) *n_nfa = reinterpret_cast<const UrlCfgDev*>(blob.data())->n_nfa;
+  return 0;
+}
+
 void ose_engine_destroy(ose_engine* eng) {
   if (!eng) return;
   Engine* e = reinterpret_cast<Engine*>(eng);
@@ -968,6 +1061,7 @@ int ose_engine_set_option(ose_engine* eng, const char* name, int64_t value) {
       {"otlp_sqlop", Engine::kOptOtlpSqlop},
       {"url_path_counts", Engine::kOptUrlPathCounts},
       {"otlp_condattr", Engine::kOptOtlpCondattr},
+      {"url_regex_nfa", Engine::kOptUrlRegexNfa},
   };
   for (const auto& o : kOpts) {
     if (strcmp(name, o.name) != 0) continue;
@@ -978,6 +1072,17 @@ int ose_engine_set_option(ose_engine* eng, const char* name, int64_t value) {
         return fail(OSE_EINVAL, "engine option otlp_condattr: odigosconditionalattributes is not configured");
       if (value)
         if (const int rc = build_condattr_keytab(e)) return rc;
+    }
+    if (o.bit == Engine::kOptUrlRegexNfa) {
+      if (!e->has_url) return fail(OSE_EINVAL, "engine option url_regex_nfa: odigosurltemplate is not configured");
+      if (value && !e->url_blob_forced_dev) {   // built once; off again goes back to the tables of ose_engine_create
+        if (int brc = bind_device(e)) return brc;
+        std::vector<uint8_t> blob;
+        uint32_t max_name = 0, words = 0;
+        if (const int rc = build_url_blob(e->url, blob, max_name, true, words)) return rc;
+        if (const int rc = upload(blob, &e->url_blob_forced_dev)) return rc;
+        e->url_forced_words = words;
+      }
     }
     if (value) e->options.fetch_or(o.bit);
     else e->options.fetch_and(~o.bit);

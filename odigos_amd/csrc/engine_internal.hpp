@@ -183,7 +183,11 @@ struct Engine {
     kOptUrlPathCounts = 32,  // run_url keeps the call's unplanned / slow list lengths (ose_engine_path_counts)
     // a feature switch like kOptOtlpSqlop: the OTLP path carries odigosconditionalattributes
     // (ose_otlp_condattr_columns, ose_otlp_encode_condattr)
-    kOptOtlpCondattr = 64
+    kOptOtlpCondattr = 64,
+    // a test and measurement seam: the URL tables rebuilt with every user
+    // regexp as an NFA program (url_blob_forced_dev), so a config whose
+    // regexps have DFAs runs both routes; set between calls, not during one
+    kOptUrlRegexNfa = 128
   };
   std::atomic<uint32_t> options{0};
   bool option(uint32_t o) const { return (options.load(std::memory_order_relaxed) & o) != 0; }
@@ -193,6 +197,14 @@ struct Engine {
 
   std::vector<uint8_t> url_blob_host;
   uint8_t* url_blob_dev = nullptr;
+  // state words of the widest NFA program in the URL tables; 0: they hold
+  // none and the stage runs as it always did
+  uint32_t url_nfa_words = 0;
+  // engine option url_regex_nfa: the all-NFA tables, built when first set
+  uint8_t* url_blob_forced_dev = nullptr;
+  uint32_t url_forced_words = 0;
+  bool url_forced() const { return option(kOptUrlRegexNfa) && url_blob_forced_dev; }
+  uint32_t url_words() const { return url_forced() ? url_forced_words : url_nfa_words; }
   std::vector<uint8_t> sampling_blob_host;   // = sampling_chunks_host[0]
   uint8_t* sampling_blob_dev = nullptr;      // = sampling_chunks_dev[0]
   // the rule tables in consecutive chunks of the level-ordered rule list,

@@ -949,6 +949,7 @@ void osehost_free(char* s) { std::free(s); }
 
 // ---- test seam: the product regex->DFA compiler evaluated on the host ----
 #include "regex_dfa.hpp"
+#include "regex_nfa.hpp"
 // One span_attribute condition on one attribute value (tests): rule_json is
 // the rule_details object, value_json an OTLP/JSON AnyValue.  1 / 0, or -1
 // with osehost_last_error() when the rule cannot be compiled.
@@ -997,6 +998,27 @@ extern "C" int osehost_regex_match(const char* pattern, const char* s, size_t n)
   if (st == ose::RegexStatus::Syntax) { g_host_err = err; return -1; }
   if (st != ose::RegexStatus::Ok) { g_host_err = err; return -2; }
   return ose::dfa_match(d, reinterpret_cast<const uint8_t*>(s), n) ? 1 : 0;
+}
+
+// The NFA route (regex_nfa.hpp): exactly the tables the URL blob gets, run
+// through the step the kernels compile.  1 / 0, -1 syntax, -2 past the NFA bound.
+extern "C" int osehost_regex_nfa_match(const char* pattern, const char* s, size_t n) {
+  ose::NfaProgram p;
+  std::string err;
+  ose::RegexStatus st = ose::compile_nfa(pattern, p, err);
+  if (st == ose::RegexStatus::Syntax) { g_host_err = err; return -1; }
+  if (st != ose::RegexStatus::Ok) { g_host_err = err; return -2; }
+  return ose::nfa_match(ose::nfa_image(p), reinterpret_cast<const uint8_t*>(s), n) ? 1 : 0;
+}
+// The rune instructions of the pattern's NFA program (tests derive bit-set
+// word edges from it); -1 / -2 as above.
+extern "C" int osehost_regex_nfa_size(const char* pattern) {
+  ose::NfaProgram p;
+  std::string err;
+  ose::RegexStatus st = ose::compile_nfa(pattern, p, err);
+  if (st == ose::RegexStatus::Syntax) { g_host_err = err; return -1; }
+  if (st != ose::RegexStatus::Ok) { g_host_err = err; return -2; }
+  return (int)p.m;
 }
 
 // The host matcher (HostRegexp) with the given full-DFA caps; *lazy = 1 when

@@ -101,6 +101,13 @@ struct UrlKernelArgs {
   uint32_t* unplanned_count;   // groups the plan kernel left to url_plan_slow_kernel (zeroed before launch)
   uint32_t* unplanned;         // [n_groups]
   uint32_t general;            // user rules or custom ids configured (selects the general kernel instances)
+  // the tables hold an NFA program (devcfg.hpp NfaDev): url_plan_kernel is
+  // not launched, url_nfa_fill_kernel lists every group and the NFA instances
+  // of the slow kernels plan and emit them per lane.  nfa_words: state words
+  // of the widest program; nfa_slab: kUrlNfaMaxWaves columns of 2 * nfa_words
+  // words per lane, word-major across the wave's lanes (workspace)
+  uint32_t nfa, nfa_words;
+  uint32_t* nfa_slab;
   // OSE_STAGE_TEMPLATE_REFS: scratch is the caller's tmpl_arena (== out_arena),
   // the fast groups' images stay where url_plan_kernel wrote them (their refs
   // point there, url_copy_kernel copies nothing).  A plan wave takes its
@@ -138,10 +145,24 @@ inline size_t url_scratch_bytes(uint64_t n, uint64_t arena_bytes) {
   const uint64_t w = g < kUrlMaxWaves ? g : kUrlMaxWaves;
   return ((arena_bytes + n + (arena_bytes + n) / 4 + 15) & ~15ull) + w * kUrlWaveSlack;
 }
-inline size_t url_workspace_bytes(uint64_t n, uint64_t arena_bytes) {
+// the NFA route's state slab: one column of 2 * nfa_words words per lane for
+// every wave of the NFA kernels' grids (at most kUrlNfaMaxWaves, and no more
+// than the batch has groups, rounded up to a workgroup of four)
+constexpr uint32_t kUrlNfaMaxWaves = 1024;
+inline uint32_t url_nfa_waves(uint64_t n) {
+  const uint64_t g = ((n + kUrlGroup - 1) / kUrlGroup + 3) & ~3ull;
+  return (uint32_t)(g < kUrlNfaMaxWaves ? g : kUrlNfaMaxWaves);
+}
+inline size_t url_nfa_slab_bytes(uint64_t n, uint32_t nfa_words) {
+  return nfa_words ? 256 + (size_t)url_nfa_waves(n) * 2 * nfa_words * kUrlGroup * 4 : 0;
+}
+// nfa_words: 0 for an engine whose URL tables hold no NFA program (its bound
+// is what it always was)
+inline size_t url_workspace_bytes(uint64_t n, uint64_t arena_bytes, uint32_t nfa_words = 0) {
   const uint64_t g = (n + kUrlGroup - 1) / kUrlGroup;
   const uint64_t t = (g + kUrlScanTile - 1) / kUrlScanTile;
-  return 16 + t * 8 + 256 + n * 16 + 8 + g * 32 + 512 + 256 + url_scratch_bytes(n, arena_bytes);
+  return 16 + t * 8 + 256 + n * 16 + 8 + g * 32 + 512 + 256 + url_scratch_bytes(n, arena_bytes) +
+         url_nfa_slab_bytes(n, nfa_words);
 }
 // refs form: the plan grid in multiples of the resident one, from the batch's
 // groups (engine.cpp run_stages); OSE_PLAN_GRID_OLD builds: 16 beside the
@@ -163,6 +184,11 @@ void launch_url_scan(const UrlKernelArgs& a, hipStream_t st);
 void launch_url_copy(const UrlKernelArgs& a, hipStream_t st);
 void launch_url_plan_slow(const UrlKernelArgs& a, hipStream_t st);
 void launch_url_emit_slow(const UrlKernelArgs& a, hipStream_t st);
+// the NFA route (UrlKernelArgs::nfa): the fill kernel in url_plan_kernel's
+// place, then the NFA instances of the two slow kernels
+void launch_url_nfa_fill(const UrlKernelArgs& a, hipStream_t st);
+void launch_url_nfa_plan(const UrlKernelArgs& a, hipStream_t st);
+void launch_url_nfa_emit(const UrlKernelArgs& a, hipStream_t st);
 
 }  // namespace ose
 

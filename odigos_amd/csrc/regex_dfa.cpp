@@ -1,5 +1,6 @@
 // regex_dfa.cpp — Go RE2-syntax regexp -> DFA (see regex_dfa.hpp).
 #include "regex_dfa.hpp"
+#include "regex_nfa.hpp"
 #include "unicode_tables.hpp"
 
 #include <algorithm>
@@ -1014,6 +1015,80 @@ bool dfa_match(const Dfa& d, const uint8_t* s, size_t n) {
     st = d.trans[(size_t)st * d.nclasses + c];
   }
   return st == d.match || d.accept_end[st];
+}
+
+// ---------------- NFA program (regex_nfa.hpp) ----------------
+// From the same Prepared as the DFA: entry j < M is rune instruction j taken
+// (the thread stands at its out), entry M the start instruction; an entry's
+// row under a context is what closure() leaves of it.
+RegexStatus compile_nfa(const std::string& pattern, NfaProgram& out, std::string& err, uint64_t max_table_bytes) {
+  max_table_bytes = std::min(max_table_bytes, NfaProgram::kMaxTableBytes);
+  Prepared P;
+  const RegexStatus pst = prepare(pattern, P, err);
+  if (pst != RegexStatus::Ok) {
+    if (pst == RegexStatus::TooLarge) err = "regexp past the NFA bound (100000 instructions): " + err;
+    return pst;
+  }
+  const Nfa& nfa = P.nfa;
+  auto too_large = [&](const std::string& what) {
+    err = "regexp past the NFA bound (" + std::to_string(max_table_bytes >> 20) + " MiB of tables): " + what;
+    return RegexStatus::TooLarge;
+  };
+  if (P.ncls > 65535) return too_large("more than 65535 rune classes");
+  out = NfaProgram{};
+  std::vector<int> rune_pc, rune_of(nfa.prog.size(), -1);
+  uint8_t ops = 0;
+  for (size_t pc = 0; pc < nfa.prog.size(); pc++) {
+    const Inst& in = nfa.prog[pc];
+    if (in.op == Inst::Rune) { rune_of[pc] = (int)rune_pc.size(); rune_pc.push_back((int)pc); }
+    if (in.op == Inst::Empty) ops |= in.eop;
+  }
+  const uint32_t M = out.m = (uint32_t)rune_pc.size();
+  const uint32_t words = out.words();
+  out.nclasses = P.ncls;
+  for (int r = 0; r < 128; r++) out.ascii[r] = (uint16_t)P.ascii[r];
+  out.hi_lo = P.hi_lo;
+  out.hi_hi = P.hi_hi;
+  out.hi_cls = P.hi_cls;
+  out.cls_type.assign(P.cls_type.begin(), P.cls_type.end());
+  uint64_t bytes = sizeof(NfaDev) + 12ull * P.hi_lo.size() + (uint64_t)P.ncls * words * 4 + P.ncls;
+  if (bytes > max_table_bytes) return too_large("the class bit sets");
+  out.in_class.assign((size_t)P.ncls * words, 0u);
+  for (uint32_t c = 0; c < P.ncls; c++)
+    for (uint32_t j = 0; j < M; j++)
+      if (P.cls_in[c][nfa.prog[rune_pc[j]].ranges]) out.in_class[(size_t)c * words + (j >> 5)] |= 1u << (j & 31);
+  // the distinct contexts, in order of first use by (prev, next)
+  std::vector<uint8_t> ctxs;
+  for (int t1 = 0; t1 < 4; t1++)
+    for (int t2 = 0; t2 < 4; t2++) {
+      const uint8_t key = context(t1, t2) & ops;
+      size_t x = std::find(ctxs.begin(), ctxs.end(), key) - ctxs.begin();
+      if (x == ctxs.size()) ctxs.push_back(key);
+      out.ctx_of[t1 * 4 + t2] = (uint8_t)x;
+    }
+  out.nctx = (uint32_t)ctxs.size();
+  const uint32_t mwords = (M + 32) / 32;
+  bytes += (uint64_t)out.nctx * ((uint64_t)(M + 2) * 4 + mwords * 4);
+  if (bytes > max_table_bytes) return too_large("the successor rows");
+  out.match.assign((size_t)out.nctx * mwords, 0u);
+  out.row.reserve((size_t)out.nctx * (M + 2));
+  std::vector<char> seen(nfa.prog.size(), 0);
+  std::vector<int> set;
+  for (uint32_t x = 0; x < out.nctx; x++) {
+    for (uint32_t j = 0; j <= M; j++) {
+      out.row.push_back((uint32_t)out.succ.size());
+      set.assign(1, j < M ? nfa.prog[rune_pc[j]].out : nfa.start);
+      bool match = false;
+      closure(nfa, set, ctxs[x], seen, match);   // (no instruction has an op outside `ops`: the masked key decides alike)
+      if (match) out.match[(size_t)x * mwords + (j >> 5)] |= 1u << (j & 31);
+      bytes += 4ull * set.size();
+      if (bytes > max_table_bytes) return too_large("the successor rows");
+      std::sort(set.begin(), set.end());
+      for (int pc : set) out.succ.push_back((uint32_t)rune_of[pc]);
+    }
+    out.row.push_back((uint32_t)out.succ.size());
+  }
+  return RegexStatus::Ok;
 }
 
 }  // namespace ose

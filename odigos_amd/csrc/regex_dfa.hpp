@@ -17,7 +17,8 @@
 // data; the reference's Go 1.25 has 15.0.0: the code points assigned in 15.0
 // are parity unpinned).
 // The device tables are bounded: a DFA above kMaxStates (about two million
-// states) or kMaxTableBytes of transitions is TooLarge for the kernels.  On
+// states) or kMaxTableBytes of transitions is TooLarge for the kernels
+// (odigosurltemplate then holds the regexp as an NFA program, regex_nfa.hpp).  On
 // the host (span_attribute json filters, the shim's predicates) HostRegexp
 // takes any such pattern with a lazy DFA (the subset construction run on
 // demand over the input, its state cache bounded and flushed as RE2's is):

@@ -25,6 +25,11 @@
 //   url_copy_kernel   template refs of the other groups and the images moved
 //                     to the compact output arena (with SIZE: the fused spans
 //                     pass of odigostrafficmetrics).
+//   url_nfa_fill_kernel, url_nfa_plan_kernel, url_nfa_emit_kernel  the route
+//                     of an engine whose tables hold an NFA program (a regexp
+//                     past the DFA bounds, regex_nfa.hpp): url_plan_kernel is
+//                     not launched, every group is listed, planned and written
+//                     per lane, the regexp call site dispatching on DFA / NFA.
 // Byte-identical to the oracle (oracle/url.c) including the compact arena.
 #include <hip/hip_runtime.h>
 
@@ -34,6 +39,7 @@
 #include "../../include/odigos_amd.h"
 #include "device_common.hpp"
 #include "kernels.hpp"
+#include "regex_nfa_device.hpp"
 #include "size_device.hpp"
 #include "url_classes.hpp"
 
@@ -198,6 +204,38 @@ struct Cfg {
   }
 };
 
+// The one regexp call site of the per-lane planners.  X = NoNfa: the tables
+// hold DFAs only (every instance but the NFA kernels').  X = NfaState: a code
+// <= -2 is NFA program -2 - code (devcfg.hpp), run by regex_nfa_device.hpp's
+// match() with the lane's two bit sets in its slab column: word k of the
+// column is col[k * kWave], so a wave's access to word k is one 256-byte row.
+struct NoNfa {};
+struct NfaState {
+  uint32_t* col;
+};
+struct SlabBits {
+  uint32_t* col;
+  __device__ __forceinline__ uint32_t at(uint32_t k) const { return col[k * kWave]; }
+  __device__ __forceinline__ void set(uint32_t k, uint32_t v) { col[k * kWave] = v; }
+};
+__device__ __forceinline__ bool rx_has(int32_t code, NoNfa) { return code >= 0; }
+__device__ __forceinline__ bool rx_has(int32_t code, NfaState) { return code != -1; }
+template <class R>
+__device__ __forceinline__ bool rx_match(const Cfg& cfg, int32_t code, R& rd, uint32_t s, uint32_t e, NoNfa) {
+  return dfa_match(cfg.blob, cfg.dfa_off(code), rd, s, e);
+}
+template <class R>
+__device__ __noinline__ bool nfa_match_at(const uint8_t* img, R& rd, uint32_t s, uint32_t e, uint32_t* col) {
+  SlabBits b{col};
+  return nfa::match(img, rd, s, e, b);
+}
+template <class R>
+__device__ __forceinline__ bool rx_match(const Cfg& cfg, int32_t code, R& rd, uint32_t s, uint32_t e, NfaState x) {
+  if (code >= 0) return dfa_match(cfg.blob, cfg.dfa_off(code), rd, s, e);
+  const uint32_t off = reinterpret_cast<const uint32_t*>(cfg.blob + cfg.h->nfa_off)[-2 - code];
+  return nfa_match_at(cfg.blob + off, rd, s, e, x.col);
+}
+
 // getSegmentTemplatizationString (templatize.go:242-269) for the segment
 // starting at s (it ends at the next '/' or n; the end is returned in *e_out):
 // the name id, or -1 when the segment stays as is.  One pass over 4-byte
@@ -206,8 +244,8 @@ struct Cfg {
 //   hex         every byte [0-9A-Fa-f] (length >= 16 and even checked after)
 //   \d{7,}      longest digit run, carried across words
 //   '@' count and "any byte >= 0x80" gate the email and U+FFFD passes.
-template <class R>
-__device__ __forceinline__ int classify_segment(const Cfg& cfg, R& rd, uint32_t s, uint32_t n, uint32_t* e_out) {
+template <class R, class X = NoNfa>
+__device__ __forceinline__ int classify_segment(const Cfg& cfg, R& rd, uint32_t s, uint32_t n, uint32_t* e_out, X x = X{}) {
   uint32_t bad_nl = 0, bad_hex = 0, any_hi = 0, ats = 0, run = 0, longnum = 0;
   auto st = rd.stream(s);
   uint32_t q = s;
@@ -243,7 +281,7 @@ __device__ __forceinline__ int classify_segment(const Cfg& cfg, R& rd, uint32_t 
   const uint32_t e = q, len = e - s;
   for (uint32_t k = 0; k < cfg.n_custom; k++) {   // custom ids first, in config order
     const UrlCustomDev& cu = reinterpret_cast<const UrlCustomDev*>(cfg.blob + cfg.h->custom_off)[k];
-    if (dfa_match(cfg.blob, cfg.dfa_off(cu.dfa), rd, s, e)) return (int)cu.name;
+    if (rx_match(cfg, cu.dfa, rd, s, e, x)) return (int)cu.name;
   }
   if (date_len(len) && date_match(rd, s, len)) return kNameDate;
   if (ats == 1 && !any_hi && email_match(rd, s, e)) return kNameEmail;
@@ -255,8 +293,8 @@ __device__ __forceinline__ int classify_segment(const Cfg& cfg, R& rd, uint32_t 
 
 // attemptTemplateWithRule (templatize.go:192-237): output body length
 // (without the leading '/') or -1.
-template <class R>
-__device__ int64_t attempt_rule(const Cfg& cfg, const UrlRuleDev& r, R& rd, uint32_t b0, uint32_t n) {
+template <class R, class X = NoNfa>
+__device__ int64_t attempt_rule(const Cfg& cfg, const UrlRuleDev& r, R& rd, uint32_t b0, uint32_t n, X x = X{}) {
   const UrlRuleSegDev* segs = reinterpret_cast<const UrlRuleSegDev*>(cfg.blob + cfg.h->segs_off) + r.seg_first;
   const uint8_t* bytes = cfg.blob + cfg.h->bytes_off;
   uint32_t s = b0;
@@ -270,7 +308,7 @@ __device__ int64_t attempt_rule(const Cfg& cfg, const UrlRuleDev& r, R& rd, uint
       for (uint32_t q = 0; q < sl; q++)
         if (bytes[sg.text_off + q] != rd.at(s + q)) return -1;
     }
-    if (sg.dfa >= 0 && !dfa_match(cfg.blob, cfg.dfa_off(sg.dfa), rd, s, e)) return -1;
+    if (rx_has(sg.dfa, x) && !rx_match(cfg, sg.dfa, rd, s, e, x)) return -1;
     if (k) len += 1;
     if (sg.kind == kRuleTemplate) len += sg.text_len + 2;
     else if (sg.kind == kRuleWildcard || sg.kind == kRuleRegex) len += sl;
@@ -384,8 +422,8 @@ struct Plan {
 };
 
 // phase 1 for one span whose path is available through rd (url_flags f)
-template <class R>
-__device__ __forceinline__ Plan plan_path(const Cfg& cfg, R& rd, uint32_t plen, uint32_t f) {
+template <class R, class X = NoNfa>
+__device__ __forceinline__ Plan plan_path(const Cfg& cfg, R& rd, uint32_t plen, uint32_t f, X x = X{}) {
   Plan p;
   const uint32_t n = path_end(rd, plen, f);
   p.lead = (n > 0 && rd.at(0) == '/') ? 1 : 0;
@@ -400,7 +438,7 @@ __device__ __forceinline__ Plan plan_path(const Cfg& cfg, R& rd, uint32_t plen, 
       const uint32_t* by_len = reinterpret_cast<const uint32_t*>(cfg.blob + cfg.h->rules_by_len_off);
       const UrlRuleDev* rules = reinterpret_cast<const UrlRuleDev*>(cfg.blob + cfg.h->rules_off);
       for (uint32_t r = by_len[nseg]; r < by_len[nseg + 1]; r++) {
-        int64_t l = attempt_rule(cfg, rules[r], rd, p.lead, n);
+        int64_t l = attempt_rule(cfg, rules[r], rd, p.lead, n, x);
         if (l >= 0) { p.mode = M_RULE; p.field = r; p.len = p.lead + (uint32_t)l; return p; }
       }
     }
@@ -409,7 +447,7 @@ __device__ __forceinline__ Plan plan_path(const Cfg& cfg, R& rd, uint32_t plen, 
   bool templated = false;
   for (;;) {
     uint32_t e;
-    const int id = classify_segment(cfg, rd, s, n, &e);
+    const int id = classify_segment(cfg, rd, s, n, &e, x);
     if (seg) l += 1;
     if (id >= 0) {
       templated = true;
@@ -430,9 +468,9 @@ __device__ __forceinline__ Plan plan_path(const Cfg& cfg, R& rd, uint32_t plen, 
 }
 
 // phase 2 for one span: writes the template through put
-template <class R, class W>
+template <class R, class W, class X = NoNfa>
 __device__ __forceinline__ void emit_path(const Cfg& cfg, R& rd, uint32_t plen, uint32_t f, uint32_t mode,
-                                          uint32_t lead, bool slow, uint32_t field, uint64_t code, W& put) {
+                                          uint32_t lead, bool slow, uint32_t field, uint64_t code, W& put, X x = X{}) {
   if (mode == M_RENAME_SLASH || mode == M_SLASH) { put.byte('/'); return; }
   if (mode == M_RULE) {
     const uint32_t n = path_end(rd, plen, f);
@@ -457,7 +495,7 @@ __device__ __forceinline__ void emit_path(const Cfg& cfg, R& rd, uint32_t plen, 
       id = (int)((code >> (seg * 4)) & 15u) - 1;
       e = id >= 0 ? scan_to(rd, s, n, '/') : copy_segment(rd, s, n, put);
     } else {
-      id = classify_segment(cfg, rd, s, n, &e);
+      id = classify_segment(cfg, rd, s, n, &e, x);
       if (id < 0) copy_range(rd, s, e, put);
     }
     if (id >= 0) put_name(cfg, (uint32_t)id, put);
@@ -807,12 +845,16 @@ __device__ __noinline__ Plan plan_global(const Cfg& cfg, const uint8_t* p, uint3
   ByteReader rd(p);
   return plan_path(cfg, rd, plen, f);
 }
-template <class R, class P>
+template <class R, class P, class X = NoNfa>
 __device__ __noinline__ void emit_out_of_line(const Cfg& cfg, R rd, uint32_t plen, uint32_t f, uint32_t mode,
                                               uint32_t lead, bool slow, uint32_t field, uint64_t code, P dst,
-                                              uint32_t cap) {
+                                              uint32_t cap, X x = X{}) {
   Put<P> put{dst, 0, cap};
-  emit_path(cfg, rd, plen, f, mode, lead, slow, field, code, put);
+  emit_path(cfg, rd, plen, f, mode, lead, slow, field, code, put, x);
+}
+__device__ __noinline__ Plan plan_global_nfa(const Cfg& cfg, const uint8_t* p, uint32_t plen, uint32_t f, NfaState x) {
+  ByteReader rd(p);
+  return plan_path(cfg, rd, plen, f, x);
 }
 
 // plan meta word: mode 3 | lead 1 | slow 1 | url_out 2 | field 25
@@ -2111,6 +2153,133 @@ __global__ __launch_bounds__(kThreads) void url_emit_slow_kernel(UrlKernelArgs a
   }
 }
 
+// ---------------------------------------------------------------------------
+// The NFA route (UrlKernelArgs::nfa: the tables hold an NFA program, which
+// K1's wave-parallel classifier cannot run).  K1 is not launched: the fill
+// kernel lists every group as unplanned, and the NFA instances of K1b and K3s
+// plan and write them per lane, the regexp call site dispatching on DFA / NFA
+// (rx_match).  A wave's slab slot holds 2 * nfa_words words per lane.
+__global__ __launch_bounds__(kThreads) void url_nfa_fill_kernel(UrlKernelArgs a) {
+  const uint32_t k = blockIdx.x * kThreads + threadIdx.x;
+  if (k < a.n_groups) a.unplanned[k] = k;
+  if (k == 0) *a.unplanned_count = a.n_groups;
+}
+
+// K1b's NFA instance: one single-wave workgroup per group (persistent), the
+// group's path bytes staged as K3s stages them (a range over the stage: HBM
+// reads), every lane planning its own span with plan_path.
+struct NfaPlanSmem {
+  NamesSmem ns;
+  __attribute__((aligned(16))) uint8_t stage[kStage + 16];
+};
+__global__ __launch_bounds__(kWave) void url_nfa_plan_kernel(UrlKernelArgs a) {
+  __shared__ NfaPlanSmem sm;
+  const uint32_t count = *a.unplanned_count;
+  if (blockIdx.x >= count) return;
+  const int lane = threadIdx.x;
+  const Cfg cfg = load_cfg(a, sm.ns);
+  lds_u32* stage32 = (lds_u32*)sm.stage;
+  const NfaState nx{a.nfa_slab + (uint64_t)blockIdx.x * 2 * a.nfa_words * kWave + lane};
+  for (uint32_t k = blockIdx.x; k < count; k += gridDim.x) {
+    const uint32_t g = a.unplanned[k];
+    const uint64_t i = (uint64_t)g * kWave + lane;
+    const PlanCols c = plan_cols(a, i);
+    const uint32_t gate = plan_gate(c);
+    Plan p;
+    uint32_t oflags = 0;
+    if (gate == 1) {
+      p.mode = M_RENAME_SLASH;
+      p.len = 1;
+      oflags = OSE_OUT_RENAME;
+    }
+    const bool reads = gate == 2 && c.pr.len;
+    uint32_t nbytes;
+    const uint32_t lo16 = stage_wave(sm.stage, a.arena, reads ? c.pr.off : ~0u, reads ? c.pr.off + c.pr.len : 0u, &nbytes);
+    if (gate == 2) {
+      if (lo16 != ~0u) {
+        LdsReader rd(stage32, reads ? c.pr.off - lo16 : 0u);
+        p = plan_path(cfg, rd, c.pr.len, c.f, nx);
+      } else {
+        p = plan_global_nfa(cfg, a.arena + c.pr.off, c.pr.len, c.f, nx);
+      }
+      oflags = OSE_OUT_SET_ATTR;                                                       // processor.go:259
+      if ((c.f & OSE_URL_NAME_EQ_METHOD) && p.len > 0) oflags |= OSE_OUT_RENAME;       // :216-225
+    }
+    wave_lds_sync();   // the stage is refilled for the next group
+    if (i < a.n_spans) {
+      a.plan_len[i] = p.len;
+      a.url_out[i] = (uint8_t)oflags;
+      a.plan_meta[i] = pack_meta(p.mode, p.lead, p.slow, oflags, p.field);
+      a.plan_code[i] = p.code;
+    }
+    const uint64_t sum = wave_sum_u64(p.len);
+    // refs form: an empty group is listed nowhere, its refs are written here
+    if (a.refs && sum == 0 && i < a.n_spans) a.tmpl[i] = ose_strref{0, 0};
+    if (lane == 0) {
+      a.group_sum[g] = sum;
+      a.group_scr[g] = ~0ull;
+      if (sum) a.slow_groups[atomicAdd(a.slow_count, 1u)] = g;
+    }
+  }
+}
+
+// K3s's NFA instance: url_emit_slow_kernel with the NFA-aware re-classification
+// (a plan marked `slow`: a hit at segment 16 or beyond, a name id over 14).
+__global__ __launch_bounds__(kThreads) void url_nfa_emit_kernel(UrlKernelArgs a) {
+  __shared__ EmitSlowSmem sm;
+  const uint32_t count = *a.slow_count;
+  if (blockIdx.x * kWaves >= count) return;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const Cfg cfg = load_cfg(a, sm.ns);
+  uint8_t* stage = sm.stage[wv];
+  lds_u32* stage32 = (lds_u32*)stage;
+  lds_w32* img = (lds_w32*)sm.img[wv];
+  const NfaState nx{a.nfa_slab + (uint64_t)(blockIdx.x * kWaves + wv) * 2 * a.nfa_words * kWave + lane};
+  for (uint32_t k = wave_first_group(); k < count; k += wave_stride()) {
+    const uint32_t g = a.slow_groups[k];
+    const uint64_t i = (uint64_t)g * kWave + lane;
+    const EmitCols c = emit_cols(a, g, lane);
+    const uint64_t base = c.base, gtotal = c.gsum;
+    const uint32_t len = c.len, meta = c.meta, mode = meta & 7u;
+    uint32_t unused;
+    const uint32_t local = wave_excl_scan(len, &unused);
+    if (a.refs && i < a.n_spans) a.tmpl[i] = ose_strref{(uint32_t)(base + local), len};
+    if (base + gtotal > a.out_cap) continue;   // overflow: the scan flagged it
+    const bool needs_path = emit_needs_path(meta);
+    const ose_strref pr = needs_path ? c.pr : ose_strref{0, 0};
+    uint32_t nbytes;
+    const uint32_t lo16 = stage_wave(stage, a.arena, needs_path ? pr.off : ~0u, needs_path ? pr.off + pr.len : 0u,
+                                     &nbytes);
+    const uint32_t shift = (uint32_t)(base & 3);
+    const uint32_t img_bytes = shift + (uint32_t)gtotal;
+    const bool direct = img_bytes > kWaveOut || lo16 == ~0u;   // wave-uniform
+    if (!direct) {
+      for (uint32_t k2 = lane; k2 < (img_bytes + 3) / 4; k2 += kWave) img[k2] = 0;
+      wave_lds_sync();
+    }
+    if (len) {
+      const uint32_t lead = (meta >> 3) & 1u, field = meta >> 7;
+      const bool slow = (meta >> 4) & 1u;
+      const uint32_t f = (needs_path && (mode == M_RULE || field == kNField)) ? a.url_flags[i] : 0u;
+      if (!direct) {
+        PutOr put(img, shift + local);
+        LdsReader rd(stage32, pr.off - lo16);
+        emit_path(cfg, rd, pr.len, f, mode, lead, slow, field, c.code, put, nx);
+        put.finish();
+      } else if (lo16 != ~0u) {
+        emit_out_of_line(cfg, LdsReader(stage32, pr.off - lo16), pr.len, f, mode, lead, slow, field, c.code,
+                         a.out_arena + base + local, len, nx);
+      } else {
+        emit_out_of_line(cfg, ByteReader(a.arena + pr.off), pr.len, f, mode, lead, slow, field, c.code,
+                         a.out_arena + base + local, len, nx);
+      }
+    }
+    wave_lds_sync();
+    if (!direct) store_image(a, img, base, shift, gtotal);
+    wave_lds_sync();   // image and stage are reused by the next group
+  }
+}
+
 // Persistent grid: as many workgroups as fit on the device at once (capped
 // by the number of groups).
 template <class K>
@@ -2207,6 +2376,30 @@ void launch_url_emit_slow(const UrlKernelArgs& a, hipStream_t st) {
   static const uint32_t cap = resident_blocks(url_emit_slow_kernel, 0);
   const uint32_t blocks = std::min<uint32_t>(cap, (a.n_groups + kWaves - 1) / kWaves);
   hipLaunchKernelGGL(url_emit_slow_kernel, dim3(blocks), dim3(kThreads), 0, st, a);
+}
+
+// The NFA kernels' grids: resident, and within the slab's wave slots
+// (url_nfa_waves: what url_workspace_bytes sized the slab for).
+void launch_url_nfa_fill(const UrlKernelArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL(url_nfa_fill_kernel, dim3((a.n_groups + kThreads - 1) / kThreads), dim3(kThreads), 0, st, a);
+}
+void launch_url_nfa_plan(const UrlKernelArgs& a, hipStream_t st) {
+  static const uint32_t cap = [] {
+    int dev = 0, cus = 0, per_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 1024u;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, url_nfa_plan_kernel, kWave, 0) != hipSuccess || per_cu <= 0)
+      per_cu = 2;
+    return (uint32_t)(cus * per_cu);
+  }();
+  const uint32_t blocks = std::min<uint32_t>({cap, a.n_groups, url_nfa_waves(a.n_spans)});
+  if (blocks) hipLaunchKernelGGL(url_nfa_plan_kernel, dim3(blocks), dim3(kWave), 0, st, a);
+}
+void launch_url_nfa_emit(const UrlKernelArgs& a, hipStream_t st) {
+  static const uint32_t cap = resident_blocks(url_nfa_emit_kernel, 0);
+  const uint32_t blocks =
+      std::min<uint32_t>({cap, (a.n_groups + kWaves - 1) / kWaves, url_nfa_waves(a.n_spans) / kWaves});
+  hipLaunchKernelGGL(url_nfa_emit_kernel, dim3(blocks), dim3(kThreads), 0, st, a);
 }
 
 }  // namespace ose

@@ -190,6 +190,7 @@ def lib() -> C.CDLL:
         "osehost_otlp_pipeline_hold": (C.c_int, [_p, C.c_uint32]),
         "osehost_otlp_pipeline_tune": (C.c_int, [_p, C.c_uint32, C.c_uint32, C.c_uint32]),
         "ose_engine_path_counts": (C.c_uint32, [_p, C.POINTER(C.c_uint64), C.c_uint32]),
+        "ose_engine_url_nfa_groups": (C.c_uint64, [_p]),
         "ose_engine_set_option": (C.c_int, [_p, C.c_char_p, C.c_int64]),
         "ose_batch_acquire": (C.c_int, [_p, C.POINTER(Columns), C.POINTER(_p)]),
         "ose_batch_columns": (C.POINTER(Columns), [_p]),
@@ -269,6 +270,10 @@ def lib() -> C.CDLL:
         "osehost_as_string": (_p, [C.c_char_p]),
         "osehost_free": (None, [_p]),
         "osehost_regex_match": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t]),
+        "osehost_regex_nfa_match": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t]),
+        "osehost_regex_nfa_size": (C.c_int, [C.c_char_p]),
+        "osehost_url_blob_hash": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                            C.POINTER(C.c_uint32)]),
         "osehost_regex_match_host": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t, C.c_uint32, C.c_uint64,
                                                C.POINTER(C.c_int)]),
         "osehost_span_attr_eval": (C.c_int, [C.c_char_p, C.c_char_p]),
