@@ -177,11 +177,7 @@ int resolve_attr_match(Engine* e, const ose_columns* c, Workspace* ws, hipStream
     a.host_mask = reinterpret_cast<const uint64_t*>(e->attr_host_mask_dev);
     a.cfg = e->attr_blob_dev;
     a.out = ws->attr_bits;
-    Engine::Timed tm{};
-    e->prof_begin("attr_eval_kernel", st, tm);
-    launch_attr_eval(a, st);
-    HIP_TRY(hipGetLastError());
-    e->prof_end(tm, st);
+    if (const int rc = e->timed("attr_eval_kernel", st, [&] { launch_attr_eval(a, st); })) return rc;
     *out = ws->attr_bits;
     return 0;
   }

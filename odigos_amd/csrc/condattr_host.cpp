@@ -221,16 +221,8 @@ int launch_both(Engine* e, const ose_condattr_columns* c, const ose_condattr_out
   a.blob = e->condattr_blob_dev;
   a.c = *c;
   a.o = *o;
-  Engine::Timed tm{};
-  e->prof_begin("condattr_scope_kernel", st, tm);
-  launch_condattr_scopes(a, st);
-  HIP_TRY(hipGetLastError());
-  e->prof_end(tm, st);
-  e->prof_begin("condattr_span_kernel", st, tm);
-  launch_condattr_spans(a, st);
-  HIP_TRY(hipGetLastError());
-  e->prof_end(tm, st);
-  return 0;
+  if (const int rc = e->timed("condattr_scope_kernel", st, [&] { launch_condattr_scopes(a, st); })) return rc;
+  return e->timed("condattr_span_kernel", st, [&] { launch_condattr_spans(a, st); });
 }
 
 // every index and string ref the kernels follow, checked on the host columns

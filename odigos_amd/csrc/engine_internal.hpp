@@ -13,6 +13,7 @@
 #include "../../include/odigos_amd.h"
 #include "config.hpp"
 #include "condattr_host.hpp"
+#include "timed_launch.hpp"
 
 namespace ose {
 
@@ -27,6 +28,7 @@ struct Engine;
 // makes the engine's device current on the calling thread (a shim's
 // goroutines migrate across OS threads; HIP's current device is per thread)
 int bind_device(const Engine* e);
+int upload(const std::vector<uint8_t>& host, uint8_t** dev);   // hipMalloc + copy
 int ensure_device();
 void engine_retain(Engine* e);
 // drops one reference; the last one synchronises the device and frees the engine
@@ -140,6 +142,9 @@ struct Workspace {
   // beside the trace stage (run_stages): fork and join events
   hipEvent_t fork = nullptr, join = nullptr, join2 = nullptr;
   bool beside_url = false;   // this call's trace stage runs beside the forked URL planning
+  Workspace() = default;
+  Workspace(const Workspace&) = delete;
+  ~Workspace();   // frees what it owns (the engine's device is current, nothing in flight)
 };
 
 struct Engine {
@@ -269,11 +274,27 @@ struct Engine {
   // ose_profile_*: (kernel name, start, stop) per launch
   bool profiling = false;
   struct Timed { const char* name; hipEvent_t a, b; };
-  std::vector<Timed> timed;
+  std::vector<Timed> timings;
   std::vector<hipEvent_t> event_pool;
+  // One launch under a profile name: `launch` queues it on st (returning
+  // nothing, or an int that ends the step when not 0), then the runtime's
+  // launch error is checked.  With profiling on, two pooled events bracket it;
+  // a failure hands them back to event_pool before its code is returned.
+  template <class F>
+  int timed(const char* name, hipStream_t st, F&& launch) {
+    return timed_launch(*this, name, st, std::forward<F>(launch));
+  }
+
+ private:
+  template <class P, class S, class F>
+  friend int timed_launch(P& p, const char* name, S st, F&& launch);
   hipEvent_t take_event();
-  void prof_begin(const char* name, hipStream_t st, Timed& t);
+  Timed prof_begin(const char* name, hipStream_t st);
   void prof_end(Timed& t, hipStream_t st);
+  void prof_drop(Timed& t);
+  int launch_status();
+
+ public:
 
   ~Engine();
   Workspace* acquire_ws(hipStream_t st);
@@ -283,6 +304,7 @@ struct Engine {
   hipStream_t take_stream();
   void give_stream(hipStream_t s);
   int build_sampling_tables();
+  int upload_sampling_tables();   // sampling_host.cpp
   int build_attr_tables();
   size_t workspace_bytes(uint64_t n_spans, uint64_t arena_bytes) const;   // every configured stage
 };
@@ -293,7 +315,30 @@ struct Engine {
 // the stream first and calls *tail before anything that reads keep
 int run_sampling(Engine* e, const ose_columns* c, const ose_outputs* o, uint32_t group_mode, const ose_rand* rnd,
                  hipStream_t st, Workspace* ws, std::function<int()>* tail = nullptr);
-size_t sampling_scratch_bytes(uint64_t n_spans);
+// One part of a stage's workspace: byte offset from the stage's base, bytes.
+struct WsPart { size_t off, bytes; };
+// the trace stage's scratch past its 256 bytes of words (sampling_host.cpp)
+struct SamplingLayout {
+  WsPart win_heads, win_base, wstatus, rec, key, k2, v2, k3, v3, hist, hoff, hstatus, long_runs, long_meta, long_pieces,
+      long_part, win_first;
+  size_t end;
+};
+SamplingLayout sampling_layout(uint64_t n_spans);
+// For the host seams the layout tests read (osehost_*_layout): a layout
+// struct is its WsParts in order, then `end`.  Returns the number of parts.
+template <class L>
+uint32_t layout_parts(const L& l, uint64_t* off, uint64_t* bytes, uint32_t cap, uint64_t* end) {
+  constexpr uint32_t kParts = (sizeof(L) - sizeof(size_t)) / sizeof(WsPart);
+  static_assert(sizeof(L) == kParts * sizeof(WsPart) + sizeof(size_t), "WsParts, then end");
+  const WsPart* p = reinterpret_cast<const WsPart*>(&l);
+  for (uint32_t k = 0; k < kParts && k < cap; k++) {
+    if (off) off[k] = p[k].off;
+    if (bytes) bytes[k] = p[k].bytes;
+  }
+  if (end) *end = l.end;
+  return kParts;
+}
+size_t sampling_scratch_bytes(uint64_t n_spans);   // = sampling_layout(n_spans).end
 // the attr_match bits the trace stage reads for this call (attr_host.cpp)
 int resolve_attr_match(Engine* e, const ose_columns* c, Workspace* ws, hipStream_t st, const uint64_t** out);
 // size stage scratch at workspace byte `off` (size_host.cpp)
@@ -304,6 +349,7 @@ int prepare_size(Engine* e, const ose_columns* c, const ose_outputs* o, uint32_t
                  const ose_rand* rnd, hipStream_t st, Workspace* ws, size_t off, SizeKernelArgs& a, bool& active);
 uint32_t* size_partials_of(Workspace* ws, size_t off, uint64_t n_scopes, uint64_t n_resources);
 int run_size_tail(Engine* e, const SizeKernelArgs& a, hipStream_t st);
+int run_size_scopes(Engine* e, const SizeKernelArgs& a, hipStream_t st);   // size_tail_kernel, size_fix_kernel
 size_t size_scratch_bytes(uint64_t n_scopes, uint64_t n_resources);
 // odigossqldboperationprocessor (sqlop_host.cpp): the SQLOP launch, the
 // columns SIZE needs after it, and run_size_tail with the spans pass that
@@ -317,7 +363,47 @@ int refuse_condattr(const char* entry);
 // every rule chunk's endpoint bits of the spans as planes of n words (a
 // config with spilled route bytes: Engine::sampling_spill), sampling_host.cpp
 int spill_endpoint_planes(Engine* e, const ose_columns* c, Workspace* ws, hipStream_t st, const uint64_t** out);
+// Where each stage's scratch starts in the one workspace of a call, and the
+// bytes the call reserves (engine.cpp; the layout is described there)
+struct StageOffsets { size_t url_off, size_off, need; };
+StageOffsets stage_offsets(uint32_t mask, bool defer, uint64_t n_spans, uint64_t n_scopes, uint64_t n_resources,
+                           uint64_t arena_bytes, uint32_t url_words);
 int run_stages(Engine* e, const ose_columns* c, const ose_outputs* o, uint32_t mask, uint32_t group_mode,
                const ose_rand* rnd, hipStream_t st);
+// odigosurltemplate (url_host.cpp): the table compiler, the stage's workspace
+// and its launches in two halves
+int build_url_blob(const UrlTemplateConfig& c, std::vector<uint8_t>& out, uint32_t& max_name, bool force_nfa,
+                   uint32_t& nfa_words);
+struct UrlLayout {
+  // the words one memset clears: [0] scan counter, [4] slow count, [8] error,
+  // [12] unplanned count, then the refs form's bump and aligned slow sum, then
+  // the scan status (8 bytes per scan tile)
+  WsPart zero, bump, slow_aligned, scan_status;
+  WsPart len, meta, code, gsum, gbase, gscr, slow, unpl, dbg;
+  WsPart scr;    // the assembled group images (refs form: none, they go to tmpl_arena)
+  WsPart slab;   // the NFA route's state slab (no NFA program: none)
+  size_t end;
+};
+UrlLayout url_layout(uint64_t n_spans, uint64_t arena_bytes, uint32_t nfa_words, bool refs);
+size_t url_workspace_bytes(uint64_t n_spans, uint64_t arena_bytes, uint32_t nfa_words = 0);   // the non-refs layout's end
+struct UrlKernelArgs;
+// What run_url takes past the workspace.  ws_off: the URL scratch starts this
+// many bytes into the workspace (past a SAMPLE stage's scratch whose slow path
+// is still to be queued).  refs: the OSE_STAGE_TEMPLATE_REFS form.  grid_mult:
+// url_plan_grid_mult's.  planned: an event recorded on st behind
+// url_plan_slow_kernel, when every span's plan_len and url_out are written
+// (all the refs form's spans pass reads).
+struct UrlRun {
+  size_t ws_off = 0;
+  bool refs = false;
+  uint32_t grid_mult = 1;
+  hipEvent_t planned = nullptr;
+};
+// the front (plan, plan_slow, scan, emit_slow); the arguments of the rest go
+// to *front, and run_url_back queues url_copy, fused with
+// odigostrafficmetrics' spans pass when front->fuse_size is set
+int run_url(Engine* e, const ose_columns* c, const ose_outputs* o, hipStream_t st, Workspace* ws, const UrlRun& r,
+            UrlKernelArgs* front);
+int run_url_back(Engine* e, const UrlKernelArgs& a, hipStream_t st);
 
 }  // namespace ose

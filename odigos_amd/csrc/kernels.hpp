@@ -133,7 +133,7 @@ constexpr uint32_t kUrlCopyMaxBlocks = 65536;
 uint32_t url_copy_blocks(uint32_t n_groups);
 constexpr uint32_t kUrlGroup = 64;       // spans per wave group (url_kernel.hip kWave)
 constexpr uint32_t kUrlScanTile = 1024;  // groups per scan workgroup (url_kernel.hip kScanThreads)
-// workspace bytes the URL stage needs for n spans (engine.cpp run_url layout)
+// (the URL stage's workspace for n spans: url_host.cpp url_layout)
 constexpr uint32_t kUrlMaxWaves = 4096;  // waves of the persistent plan grid (>= its resident waves)
 constexpr uint32_t kUrlWaveSlack = 8192; // scratch bytes per wave on top of its share
 // scratch for the assembled group images of a batch whose arena holds
@@ -155,14 +155,6 @@ inline uint32_t url_nfa_waves(uint64_t n) {
 }
 inline size_t url_nfa_slab_bytes(uint64_t n, uint32_t nfa_words) {
   return nfa_words ? 256 + (size_t)url_nfa_waves(n) * 2 * nfa_words * kUrlGroup * 4 : 0;
-}
-// nfa_words: 0 for an engine whose URL tables hold no NFA program (its bound
-// is what it always was)
-inline size_t url_workspace_bytes(uint64_t n, uint64_t arena_bytes, uint32_t nfa_words = 0) {
-  const uint64_t g = (n + kUrlGroup - 1) / kUrlGroup;
-  const uint64_t t = (g + kUrlScanTile - 1) / kUrlScanTile;
-  return 16 + t * 8 + 256 + n * 16 + 8 + g * 32 + 512 + 256 + url_scratch_bytes(n, arena_bytes) +
-         url_nfa_slab_bytes(n, nfa_words);
 }
 // refs form: the plan grid in multiples of the resident one, from the batch's
 // groups (engine.cpp run_stages); OSE_PLAN_GRID_OLD builds: 16 beside the

@@ -46,12 +46,7 @@ int condattr_spans(Engine* e, OtlpBatchImpl* b, uint64_t n, const uint64_t* span
   a.span_val = const_cast<ose_strref*>(ca.span_val);
   a.span_kv_size = const_cast<uint32_t*>(ca.span_kv_size);
   set_host_list(a, hl);
-  Engine::Timed tm{};
-  e->prof_begin("otlp_condattr_kernel", st, tm);
-  launch_otlp_condattr(a, st);
-  HIP_TRY(hipGetLastError());
-  e->prof_end(tm, st);
-  return 0;
+  return e->timed("otlp_condattr_kernel", st, [&] { launch_otlp_condattr(a, st); });
 }
 
 // The rest, after the host pass: the K entries of every listed span (pb_span

@@ -1325,11 +1325,10 @@ int span_kernels(Engine* e, OtlpEngine* o, OtlpBatchImpl* b, uint64_t n, const u
   set_span_columns(a, c);
   set_host_list(a, hl);
   (void)hipGetLastError();   // a stale error of an earlier call must not be reported as this launch's
-  Engine::Timed tm{};
-  e->prof_begin("otlp_span_kernel", st, tm);
-  if (n) b->walk_info[6] = launch_otlp_spans(a, st);
-  HIP_TRY(hipGetLastError());
-  e->prof_end(tm, st);
+  if (const int rc = e->timed("otlp_span_kernel", st, [&] {
+        if (n) b->walk_info[6] = launch_otlp_spans(a, st);
+      }))
+    return rc;
   if (sql && n) {   // db_flags / db_query: a pass of its own (the span kernels stay within their register budget)
     OtlpSqlArgs qa{};
     qa.pb = b->arena.p;
@@ -1338,11 +1337,7 @@ int span_kernels(Engine* e, OtlpEngine* o, OtlpBatchImpl* b, uint64_t n, const u
     qa.db_flags = const_cast<uint8_t*>(c.db_flags);
     qa.db_query = const_cast<ose_strref*>(c.db_query);
     set_host_list(qa, hl);
-    Engine::Timed tq{};
-    e->prof_begin("otlp_sqlop_kernel", st, tq);
-    launch_otlp_sqlop(qa, st);
-    HIP_TRY(hipGetLastError());
-    e->prof_end(tq, st);
+    if (const int rc = e->timed("otlp_sqlop_kernel", st, [&] { launch_otlp_sqlop(qa, st); })) return rc;
   }
   if (ca)
     if (int rc = condattr_spans(e, b, n, span_ref, hl, st)) return rc;

@@ -12,11 +12,11 @@
 #include "engine_internal.hpp"
 #include "host.hpp"
 #include "kernels.hpp"
+#include "slab.hpp"
 
 namespace ose {
 
 namespace {
-size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 uint64_t windows_of(uint64_t n) { return std::max<uint64_t>(1, (n + 63) / 64); }
 uint64_t table_slots(uint64_t n) {
   uint64_t cap = 1024;
@@ -262,43 +262,110 @@ int Engine::build_sampling_tables() {
   return 0;
 }
 
-// Scratch of the trace stage for n spans (run_sampling layout).
-size_t sampling_scratch_bytes(uint64_t n) {
+// The rule tables on the device (ose_engine_create, after
+// build_sampling_tables): every chunk's table, the chunk-local service maps,
+// and the trace-id exchange tables.
+int Engine::upload_sampling_tables() {
+  if (!has_sampling) return 0;
+  int rc = 0;
+  sampling_chunks_dev.assign(sampling_chunks_host.size(), nullptr);
+  for (size_t k = 0; k < sampling_chunks_host.size(); k++) {
+    rc = upload(sampling_chunks_host[k], &sampling_chunks_dev[k]);
+    if (rc) return rc;
+  }
+  sampling_blob_dev = sampling_chunks_dev[0];
+  sampling_svc_map_dev.assign(sampling_svc_map_host.size(), nullptr);
+  for (size_t k = 0; k < sampling_svc_map_host.size(); k++) {
+    const auto& m = sampling_svc_map_host[k];
+    std::vector<uint8_t> raw(reinterpret_cast<const uint8_t*>(m.data()),
+                             reinterpret_cast<const uint8_t*>(m.data()) + 4 * m.size());
+    rc = upload(raw, reinterpret_cast<uint8_t**>(&sampling_svc_map_dev[k]));
+    if (rc) return rc;
+  }
+  if (!sampling_svc_map_dev.empty()) {
+    std::vector<uint8_t> raw(sizeof(uint32_t*) * sampling_svc_map_dev.size());
+    std::memcpy(raw.data(), sampling_svc_map_dev.data(), raw.size());
+    rc = upload(raw, reinterpret_cast<uint8_t**>(&sampling_svc_maps_dev));
+    if (rc) return rc;
+  }
+  const size_t K = sampling_chunks_dev.size(), L = sampling_lat_svc.size();
+  // then trace_multi_kernel's latency-service ids: [n_services] the index of
+  // each service among those with http_latency rules in any chunk (or
+  // 0xFFFFFFFF), [64] the service of each index
+  const size_t S = service_ids.size();
+  std::vector<uint32_t> gof(S, 0xFFFFFFFFu), gsvc(64, 0);
+  uint32_t ng = 0;
+  for (size_t v = 0; v < S; v++)
+    if ((sampling_lat_svc[v >> 5] >> (v & 31)) & 1u) {
+      if (ng < 64) {
+        gof[v] = ng;
+        gsvc[ng] = (uint32_t)v;
+      }
+      ng++;
+    }
+  sampling_n_lat_svc = ng;
+  // then each chunk's SampWalkDev (chunks of <= 128 rules; trace_multi_kernel)
+  std::vector<SampWalkDev> walks(K);
+  sampling_walk_ok = true;
+  for (size_t k = 0; k < K; k++) {
+    SampWalkDev& w = walks[k];
+    std::memset(&w, 0, sizeof w);
+    const uint8_t* b = sampling_chunks_host[k].data();
+    const SampCfgDev* h = reinterpret_cast<const SampCfgDev*>(b);
+    if (h->n_rules > 128) sampling_walk_ok = false;
+    const SampRuleDev* rules = reinterpret_cast<const SampRuleDev*>(b + h->rules_off);
+    for (uint32_t r = 0; r < h->n_rules && r < 128; r++) {
+      const uint64_t bit = 1ull << (r & 63);
+      if (rules[r].type == kSampError) w.err[r >> 6] |= bit;
+      else if (rules[r].type == kSampLatency) w.lat_rule[rules[r].bit & 63] = (uint8_t)r;
+      else w.svc[rules[r].bit & 63][r >> 6] |= bit;
+    }
+  }
+  const size_t wo = up(8 * K + 4 * L + 4 * S + 4 * 64, 16);
+  std::vector<uint8_t> st(wo + K * sizeof(SampWalkDev));
+  std::memcpy(st.data(), sampling_chunks_dev.data(), 8 * K);
+  std::memcpy(st.data() + 8 * K, sampling_lat_svc.data(), 4 * L);
+  if (S) std::memcpy(st.data() + 8 * K + 4 * L, gof.data(), 4 * S);
+  std::memcpy(st.data() + 8 * K + 4 * L + 4 * S, gsvc.data(), 4 * 64);
+  std::memcpy(st.data() + wo, walks.data(), K * sizeof(SampWalkDev));
+  rc = upload(st, &shard_tables_dev);
+  if (rc) return rc;
+  return 0;
+}
+
+// The trace stage's scratch for n spans: [0, 256) the stage's words (misc),
+// then every part on a 256-byte boundary, then 256 spare bytes.  The bound
+// and run_sampling_pass's pointers both come from here.
+SamplingLayout sampling_layout(uint64_t n) {
   const uint64_t W = windows_of(n);
   const uint64_t N = std::max<uint64_t>(n, 1);
   const uint64_t T = (N + kSortTile - 1) / kSortTile;
   const uint64_t wtiles = (W + kScanTileItems - 1) / kScanTileItems;
   const uint64_t htiles = (256 * T + kScanTileItems - 1) / kScanTileItems;
-  size_t s = 256;
-  s = align_up(s + 8 * W, 256);        // win_heads
-  s = align_up(s + 4 * W, 256);        // win_base
-  s = align_up(s + 8 * wtiles, 256);   // scan status (windows)
-  s = align_up(s + 16 * N, 256);       // rec
-  s = align_up(s + 4 * N, 256) * 1;    // key
-  s = align_up(s + 4 * N, 256);        // keys2
-  s = align_up(s + 4 * N, 256);        // vals
-  s = align_up(s + 4 * N, 256);        // keys3
-  s = align_up(s + 4 * N, 256);        // vals2
-  s = align_up(s + 4 * 256 * T, 256);  // hist
-  s = align_up(s + 4 * 256 * T, 256);  // hist offsets
-  s = align_up(s + 8 * htiles, 256);   // scan status (hist)
-  s = align_up(s + 4 * (N / 64 + 1), 256);   // long runs
-  s = align_up(s + 16 * (N / 64 + 1), 256);  // long-run meta
-  s = align_up(s + 8 * long_piece_cap(N), 256);   // long-run pieces
-  s = align_up(s + (size_t)kLongPartBytes * long_part_cap(N), 256);   // piece partials
-  s = align_up(s + 8 * W, 256);        // win_first (run-list path)
-  return s + 256;
+  Carve c{256};
+  auto part = [&](size_t bytes) { return WsPart{c.take(bytes), bytes}; };
+  SamplingLayout L;
+  L.win_heads = part(8 * W);
+  L.win_base = part(4 * W);
+  L.wstatus = part(8 * wtiles);   // scan status (windows)
+  L.rec = part(16 * N);
+  L.key = part(4 * N);
+  L.k2 = part(4 * N);
+  L.v2 = part(4 * N);
+  L.k3 = part(4 * N);
+  L.v3 = part(4 * N);
+  L.hist = part(4 * 256 * T);
+  L.hoff = part(4 * 256 * T);     // hist offsets
+  L.hstatus = part(8 * htiles);   // scan status (hist)
+  L.long_runs = part(4 * (N / 64 + 1));
+  L.long_meta = part(16 * (N / 64 + 1));
+  L.long_pieces = part(8 * long_piece_cap(N));
+  L.long_part = part((size_t)kLongPartBytes * long_part_cap(N));   // piece partials
+  L.win_first = part(8 * W);      // run-list path
+  L.end = up(c.off) + 256;
+  return L;
 }
-
-// the workspace of a call running every configured stage (run_stages'
-// layout: SAMPLE's scratch, the URL scratch after it, the size sums after
-// that; scopes and resources bounded by the spans)
-size_t Engine::workspace_bytes(uint64_t n_spans, uint64_t arena_bytes) const {
-  size_t s = has_sampling ? align_up(sampling_scratch_bytes(n_spans), 256) : 0;
-  if (has_url) s = align_up(s + url_workspace_bytes(n_spans, arena_bytes, url_words()), 256);
-  if (has_traffic) s += size_scratch_bytes(n_spans, n_spans);
-  return s;
-}
+size_t sampling_scratch_bytes(uint64_t n) { return sampling_layout(n).end; }
 
 // Run lists of the run-list path (allocated the first time a batch repeats
 // a trace id; sized like the exact table).
@@ -360,7 +427,7 @@ uint32_t multi_cfg_bytes(const Engine* e) {
     const uint32_t nb = std::min<uint32_t>(reinterpret_cast<const SampCfgDev*>(h.data())->total_bytes, kSampCfgLds);
     t += (nb + 15u) & ~15u;
   }
-  return t + (uint32_t)align_up(4 * e->service_ids.size() + 4 * 64, 16) +
+  return t + (uint32_t)up(4 * e->service_ids.size() + 4 * 64, 16) +
          (uint32_t)(e->sampling_chunks_host.size() * sizeof(SampWalkDev));
 }
 // trace_multi_kernel takes the call: 2..kMaxMulti chunks whose tables fit
@@ -404,8 +471,8 @@ int run_sampling_pass(Engine* e, const ose_columns* c, const ose_outputs* o, uin
   const uint64_t T = (N + kSortTile - 1) / kSortTile;
   const uint32_t wtiles = (uint32_t)((W + kScanTileItems - 1) / kScanTileItems);
   const uint32_t htiles = (uint32_t)((256 * T + kScanTileItems - 1) / kScanTileItems);
-  const size_t need = sampling_scratch_bytes(n);
-  int rc = ws->reserve(need);
+  const SamplingLayout L = sampling_layout(n);
+  int rc = ws->reserve(L.end);
   if (rc) return rc;
   if (group_mode == OSE_GROUP_TRACE_ID) {
     rc = ws->reserve_table(n);
@@ -418,31 +485,24 @@ int run_sampling_pass(Engine* e, const ose_columns* c, const ose_outputs* o, uin
     }
   }
   uint8_t* base = static_cast<uint8_t*>(ws->dev);
-  size_t off = 256;
-  auto take = [&](size_t bytes) {
-    uint8_t* p = base + off;
-    off = align_up(off + bytes, 256);
-    return p;
-  };
   uint32_t* misc = reinterpret_cast<uint32_t*>(base);   // [0] dup, [2] scan counter (windows), [4] scan counter (hist), [12] long runs, [13] their pieces, [14] run-list overflow, [15] piece partials
-  uint64_t* win_heads = reinterpret_cast<uint64_t*>(take(8 * W));
-  uint32_t* win_base = reinterpret_cast<uint32_t*>(take(4 * W));
-  uint64_t* wstatus = reinterpret_cast<uint64_t*>(take(8 * (size_t)wtiles));
-  TraceRec* rec = reinterpret_cast<TraceRec*>(take(16 * N));
-  uint32_t* key = reinterpret_cast<uint32_t*>(take(4 * N));
-  uint32_t* k2 = reinterpret_cast<uint32_t*>(take(4 * N));
-  uint32_t* v2 = reinterpret_cast<uint32_t*>(take(4 * N));
-  uint32_t* k3 = reinterpret_cast<uint32_t*>(take(4 * N));
-  uint32_t* v3 = reinterpret_cast<uint32_t*>(take(4 * N));
-  uint32_t* hist = reinterpret_cast<uint32_t*>(take(4 * 256 * T));
-  uint32_t* hoff = reinterpret_cast<uint32_t*>(take(4 * 256 * T));
-  uint64_t* hstatus = reinterpret_cast<uint64_t*>(take(8 * (size_t)htiles));
-  uint32_t* long_runs = reinterpret_cast<uint32_t*>(take(4 * (N / 64 + 1)));
-  uint4* long_meta = reinterpret_cast<uint4*>(take(16 * (N / 64 + 1)));
-  uint2* long_pieces = reinterpret_cast<uint2*>(take(8 * long_piece_cap(N)));
-  uint8_t* long_part = take((size_t)kLongPartBytes * long_part_cap(N));
-  uint64_t* win_first = reinterpret_cast<uint64_t*>(take(8 * W));
-  if (off > need) return fail(OSE_EINVAL, "internal: trace workspace layout exceeds its bound");
+  uint64_t* win_heads = reinterpret_cast<uint64_t*>(base + L.win_heads.off);
+  uint32_t* win_base = reinterpret_cast<uint32_t*>(base + L.win_base.off);
+  uint64_t* wstatus = reinterpret_cast<uint64_t*>(base + L.wstatus.off);
+  TraceRec* rec = reinterpret_cast<TraceRec*>(base + L.rec.off);
+  uint32_t* key = reinterpret_cast<uint32_t*>(base + L.key.off);
+  uint32_t* k2 = reinterpret_cast<uint32_t*>(base + L.k2.off);
+  uint32_t* v2 = reinterpret_cast<uint32_t*>(base + L.v2.off);
+  uint32_t* k3 = reinterpret_cast<uint32_t*>(base + L.k3.off);
+  uint32_t* v3 = reinterpret_cast<uint32_t*>(base + L.v3.off);
+  uint32_t* hist = reinterpret_cast<uint32_t*>(base + L.hist.off);
+  uint32_t* hoff = reinterpret_cast<uint32_t*>(base + L.hoff.off);
+  uint64_t* hstatus = reinterpret_cast<uint64_t*>(base + L.hstatus.off);
+  uint32_t* long_runs = reinterpret_cast<uint32_t*>(base + L.long_runs.off);
+  uint4* long_meta = reinterpret_cast<uint4*>(base + L.long_meta.off);
+  uint2* long_pieces = reinterpret_cast<uint2*>(base + L.long_pieces.off);
+  uint8_t* long_part = base + L.long_part.off;
+  uint64_t* win_first = reinterpret_cast<uint64_t*>(base + L.win_first.off);
   uint32_t* err = o->device_status ? o->device_status : misc + 8;
   // a later rule-chunk pass keeps the first pass's *dup (misc[0]): the batch's
   // trace-id layout is the same, so it neither registers run heads nor checks
@@ -520,7 +580,7 @@ int run_sampling_pass(Engine* e, const ose_columns* c, const ose_outputs* o, uin
     a.lat_gslot = reinterpret_cast<const uint32_t*>(e->shard_tables_dev + 8 * e->sampling_chunks_dev.size() +
                                                     4 * e->sampling_lat_svc.size());
     a.walks = reinterpret_cast<const SampWalkDev*>(
-        e->shard_tables_dev + align_up(8 * e->sampling_chunks_dev.size() + 4 * e->sampling_lat_svc.size() +
+        e->shard_tables_dev + up(8 * e->sampling_chunks_dev.size() + 4 * e->sampling_lat_svc.size() +
                                            4 * e->service_ids.size() + 4 * 64, 16));
   }
   a.long_steps = kLongSteps;
@@ -557,26 +617,13 @@ int run_sampling_pass(Engine* e, const ose_columns* c, const ose_outputs* o, uin
     a.dup_bkt_bits = ws->dup_bkt_bits;
     HIP_TRY(hipMemsetAsync(a.dup_bkt_count, 0, sizeof(uint32_t) << a.dup_bkt_bits, st));
   }
-  Engine::Timed tm{};
-  e->prof_begin(multi ? "trace_multi_kernel" : "trace_eval_kernel", st, tm);
-  launch_trace_eval(a, st);
-  HIP_TRY(hipGetLastError());
-  e->prof_end(tm, st);
-  if (a.dup_bkt) {
-    Engine::Timed td{};
-    e->prof_begin("trace_dup_check", st, td);
-    launch_trace_dup_check(a, st);
-    HIP_TRY(hipGetLastError());
-    e->prof_end(td, st);
-  }
+  if ((rc = e->timed(multi ? "trace_multi_kernel" : "trace_eval_kernel", st, [&] { launch_trace_eval(a, st); }))) return rc;
+  if (a.dup_bkt)
+    if ((rc = e->timed("trace_dup_check", st, [&] { launch_trace_dup_check(a, st); }))) return rc;
   auto long_pass = [=](uint32_t known_runs) -> int {
     e->long_run_passes.fetch_add(1, std::memory_order_relaxed);
-    Engine::Timed tl{};
-    e->prof_begin("trace_long_kernel", st, tl);
-    launch_trace_long(a, st, known_runs);   // (trace_long_plan_kernel, then the pieces)
-    HIP_TRY(hipGetLastError());
-    e->prof_end(tl, st);
-    return 0;
+    // (trace_long_plan_kernel, then the pieces)
+    return e->timed("trace_long_kernel", st, [&] { launch_trace_long(a, st, known_runs); });
   };
   // host-gated (tail): queued only when the fast path listed long runs
   const bool gate_long = tail && group_mode == OSE_GROUP_TRACE_ID;
@@ -602,17 +649,16 @@ int run_sampling_pass(Engine* e, const ose_columns* c, const ose_outputs* o, uin
     rl.path_count = e->path_count_dev;
     rl.win_first = win_first;
     rl.head_slot = key;
-    Engine::Timed tr{};
-    e->prof_begin("trace_run_list", st, tr);
-    launch_trace_runs(rl, st);
-    HIP_TRY(hipGetLastError());
-    launch_trace_fold(rl, st);
-    HIP_TRY(hipGetLastError());
-    launch_trace_first_select(rl, st);
-    HIP_TRY(hipGetLastError());
-    e->prof_end(tr, st);
-    Engine::Timed ts{};
-    e->prof_begin("trace_sort_path", st, ts);
+    rr = e->timed("trace_run_list", st, [&]() -> int {
+      launch_trace_runs(rl, st);
+      HIP_TRY(hipGetLastError());
+      launch_trace_fold(rl, st);
+      HIP_TRY(hipGetLastError());
+      launch_trace_first_select(rl, st);
+      return 0;
+    });
+    if (rr) return rr;
+    rr = e->timed("trace_sort_path", st, [&]() -> int {
     TraceSortArgs s{};
     s.n_spans = n;
     s.n_tiles = (uint32_t)T;
@@ -672,8 +718,9 @@ int run_sampling_pass(Engine* e, const ose_columns* c, const ose_outputs* o, uin
     b.perm = vin;
     b.key = key;
     launch_trace_eval(b, st);
-    HIP_TRY(hipGetLastError());
-    e->prof_end(ts, st);
+    return 0;
+    });
+    if (rr) return rr;
   }
 
   if (per_trace) {
@@ -838,3 +885,35 @@ int run_sampling(Engine* e, const ose_columns* c, const ose_outputs* o, uint32_t
 }
 
 }  // namespace ose
+
+using namespace ose;
+
+// Diagnostic, no device: the trace stage's workspace for n spans, part by
+// part in SamplingLayout's order (the 256 bytes of words at offset 0 are no
+// part); returns the number of parts.
+extern "C" uint32_t osehost_sampling_layout(uint64_t n_spans, uint64_t* off, uint64_t* bytes, uint32_t cap, uint64_t* end) {
+  return layout_parts(sampling_layout(n_spans), off, bytes, cap, end);
+}
+
+// Diagnostic, no device: the number of rule chunks build_sampling_tables
+// cuts the config's odigossampling rule list into (0 without the section);
+// the codes and messages of ose_engine_create's sampling checks.
+extern "C" int osehost_sampling_chunks(const char* cfg_json, uint32_t* n_chunks) {
+  if (!n_chunks) return fail(OSE_EINVAL, "n_chunks is NULL");
+  *n_chunks = 0;
+  Json root;
+  try {
+    root = parse_json(cfg_json ? cfg_json : "{}");
+  } catch (const std::exception& ex) {
+    return fail(OSE_EINVAL, ex.what());
+  }
+  const Json* j = root.is_obj() ? root.get("odigossampling") : nullptr;
+  if (!j) return 0;
+  Engine e;
+  const std::string err = decode_sampling_config(*j, e.sampling);
+  if (!err.empty()) return fail(OSE_EINVAL, err);
+  e.has_sampling = true;
+  if (const int rc = e.build_sampling_tables()) return rc;
+  *n_chunks = (uint32_t)e.sampling_chunks_host.size();
+  return 0;
+}

@@ -21,11 +21,10 @@
 #include "devcfg.hpp"
 #include "engine_internal.hpp"
 #include "kernels.hpp"
+#include "slab.hpp"
 
 namespace ose {
 namespace {
-size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 // RCCL, resolved at run time: the process's already loaded copy when there
 // is one (PyTorch loads its own), else the system librccl.  Nothing links
 // against it, so the library still loads where RCCL is absent.
@@ -348,9 +347,11 @@ int owner_decide(Engine* e, XScratch* xs, const uint8_t* recvb, uint64_t n_recv,
   if (!n_recv) return 0;
   const uint64_t RB = x_rec_bytes(K);
   const uint64_t B = std::max<uint64_t>(1, (n_recv + kOwnerAvg - 1) / kOwnerAvg);
-  const size_t off_rec = align_up(64 + 4 * B, 256);
+  Carve bk{64};   // [0, 64) the overflow word | the bucket counts | the bucket records
+  bk.take(4 * B, 4);
+  const size_t off_rec = bk.take(8 * kOwnerSlotWords * B * kOwnerCap);
   int rc;
-  if ((rc = xs->bkt.need(off_rec + 8 * kOwnerSlotWords * B * kOwnerCap))) return rc;
+  if ((rc = xs->bkt.need(bk.off))) return rc;
   if (!xs->host_flag) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&xs->host_flag), 64, hipHostMallocDefault));
   uint8_t* bb = xs->bkt.as<uint8_t>();
   OwnerArgs oa{};
@@ -379,12 +380,11 @@ int owner_decide(Engine* e, XScratch* xs, const uint8_t* recvb, uint64_t n_recv,
     oa.clocks = clocks;
   }
 #endif
-  Engine::Timed tf{};
-  e->prof_begin("owner_fold", st, tf);
-  launch_owner_bucket(oa, st);
-  launch_owner_fold(oa, st);
-  e->prof_end(tf, st);
-  HIP_TRY(hipGetLastError());
+  rc = e->timed("owner_fold", st, [&] {
+    launch_owner_bucket(oa, st);
+    launch_owner_fold(oa, st);
+  });
+  if (rc) return rc;
 #if OSE_DIAG
   if (oa.clocks) {
     uint64_t h[8];
@@ -403,11 +403,11 @@ int owner_decide(Engine* e, XScratch* xs, const uint8_t* recvb, uint64_t n_recv,
   // the general path: owner-side columns (trace_id 16, start 8, end 8, route_match 8 K, svc_match 8 K,
   // resource 4, res_svc 4, res_svc_str 4, status 1 per record)
   const uint64_t R = n_recv;
-  const size_t o_tid = 0, o_st = align_up(o_tid + 16 * R, 256), o_en = align_up(o_st + 8 * R, 256),
-               o_rm = align_up(o_en + 8 * R, 256), o_sm = align_up(o_rm + 8 * R * K, 256),
-               o_res = align_up(o_sm + 8 * R * K, 256), o_sv = align_up(o_res + 4 * R, 256),
-               o_ss = align_up(o_sv + 4 * R, 256), o_stat = align_up(o_ss + 4 * R, 256), o_end = o_stat + R + 256;
-  if ((rc = xs->cols.need(o_end))) return rc;
+  Carve oc_at;
+  const size_t o_tid = oc_at.take(16 * R), o_st = oc_at.take(8 * R), o_en = oc_at.take(8 * R),
+               o_rm = oc_at.take(8 * R * K), o_sm = oc_at.take(8 * R * K), o_res = oc_at.take(4 * R),
+               o_sv = oc_at.take(4 * R), o_ss = oc_at.take(4 * R), o_stat = oc_at.take(R + 256);
+  if ((rc = xs->cols.need(oc_at.off))) return rc;
   uint8_t* cb = xs->cols.as<uint8_t>();
   ose_columns oc{};
   oc.n_spans = n_recv;
@@ -422,23 +422,19 @@ int owner_decide(Engine* e, XScratch* xs, const uint8_t* recvb, uint64_t n_recv,
   oc.res_svc = reinterpret_cast<uint32_t*>(cb + o_sv);
   oc.res_svc_str = reinterpret_cast<uint32_t*>(cb + o_ss);
   oc.status = cb + o_stat;
-  Engine::Timed tm{};
-  e->prof_begin("shard_unpack", st, tm);
-  rc = ose_shard_unpack(recvb, n_recv, (uint32_t)RB, const_cast<uint64_t*>(oc.trace_id), const_cast<uint64_t*>(oc.start_ns),
+  rc = e->timed("shard_unpack", st, [&] {
+    return ose_shard_unpack(recvb, n_recv, (uint32_t)RB, const_cast<uint64_t*>(oc.trace_id), const_cast<uint64_t*>(oc.start_ns),
                         const_cast<uint64_t*>(oc.end_ns), const_cast<uint8_t*>(oc.status),
                         const_cast<uint32_t*>(oc.resource), const_cast<uint32_t*>(oc.res_svc),
                         const_cast<uint32_t*>(oc.res_svc_str), const_cast<uint64_t*>(oc.route_match),
                         const_cast<uint64_t*>(oc.svc_match), st);
-  e->prof_end(tm, st);
+  });
   if (rc) return rc;
   ose_outputs ox{};
   ox.keep = keep;
   ox.device_status = device_status;
-  Engine::Timed to{};
-  e->prof_begin("owner_sample", st, to);
-  rc = run_stages(e, &oc, &ox, OSE_STAGE_SAMPLE, OSE_GROUP_TRACE_ID, rnd, st);
-  e->prof_end(to, st);
-  return rc;
+  return e->timed("owner_sample", st,
+                  [&] { return run_stages(e, &oc, &ox, OSE_STAGE_SAMPLE, OSE_GROUP_TRACE_ID, rnd, st); });
 }
 
 // One exchange round (ose_exchange_sample).  Everything that can fail on
@@ -559,8 +555,9 @@ int ose_shard_pack(ose_engine* eng, const ose_columns* c, uint32_t n_ranks, void
   const uint64_t H = (uint64_t)n_ranks * T;
   const uint32_t htiles = (uint32_t)((H + kScanTileItems - 1) / kScanTileItems);
   Workspace* ws = e->acquire_ws(st);
-  const size_t off_hist = 256, off_hoff = align_up(off_hist + 4 * H, 256), off_st = align_up(off_hoff + 4 * H, 256);
-  int rc = ws->reserve(off_st + 8 * (size_t)htiles + 256);
+  Carve hc{256};   // [0, 256) the pack's words | hist | hist offsets | scan status | 256 spare
+  const size_t off_hist = hc.take(4 * H), off_hoff = hc.take(4 * H), off_st = hc.take(8 * (size_t)htiles + 256);
+  int rc = ws->reserve(hc.off);
   if (rc) {
     e->release_ws(ws, st);
     return rc;
@@ -635,9 +632,6 @@ int ose_shard_pack(ose_engine* eng, const ose_columns* c, uint32_t n_ranks, void
       rc = fail(OSE_EDEVICE, "hipMemsetAsync failed");
       break;
     }
-    Engine::Timed tm{};
-    e->prof_begin("shard_pack", st, tm);
-    launch_shard_hist(a, st);
     ScanArgs sa{};
     sa.n = H;
     sa.n_tiles = htiles;
@@ -646,11 +640,13 @@ int ose_shard_pack(ose_engine* eng, const ose_columns* c, uint32_t n_ranks, void
     sa.counter = reinterpret_cast<uint32_t*>(base) + 2;
     sa.status = reinterpret_cast<uint64_t*>(base + off_st);
     sa.error = err;
-    launch_scan_u32(sa, st);
-    launch_shard_counts(a, st);
-    launch_shard_scatter(a, st);
-    e->prof_end(tm, st);
-    if (hipGetLastError() != hipSuccess) rc = fail(OSE_EDEVICE, "shard pack launch failed");
+    rc = e->timed("shard_pack", st, [&] {
+      launch_shard_hist(a, st);
+      launch_scan_u32(sa, st);
+      launch_shard_counts(a, st);
+      launch_shard_scatter(a, st);
+    });
+    if (rc) rc = fail(OSE_EDEVICE, "shard pack launch failed");
   } while (0);
   e->release_ws(ws, st);
   return rc;

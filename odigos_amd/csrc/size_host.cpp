@@ -4,12 +4,9 @@
 
 #include "engine_internal.hpp"
 #include "kernels.hpp"
+#include "slab.hpp"
 
 namespace ose {
-
-namespace {
-size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-}  // namespace
 
 // [256 | scope sums 8·S | window parts 32·W | window fix flags 4·W | kept
 // partials 4·kUrlCopyMaxBlocks | 256], W = the 64-scope windows
@@ -21,10 +18,10 @@ SizeLayout size_layout(uint64_t n_scopes) {
   const uint64_t W = (std::max<uint64_t>(n_scopes, 1) + 63) / 64;
   SizeLayout L;
   L.scope = 256;
-  L.parts = align_up(L.scope + 8 * std::max<uint64_t>(n_scopes, 1), 256);
-  L.fix = align_up(L.parts + 32 * W, 256);
-  L.partials = align_up(L.fix + 4 * W, 256);
-  L.end = align_up(L.partials + 4ull * kUrlCopyMaxBlocks, 256) + 256;
+  L.parts = up(L.scope + 8 * std::max<uint64_t>(n_scopes, 1));
+  L.fix = up(L.parts + 32 * W);
+  L.partials = up(L.fix + 4 * W);
+  L.end = up(L.partials + 4ull * kUrlCopyMaxBlocks) + 256;
   return L;
 }
 }  // namespace
@@ -112,22 +109,14 @@ uint32_t* size_partials_of(Workspace* ws, size_t off, uint64_t n_scopes, uint64_
 // the spans pass (unless url_copy_kernel ran it: a.kept_partials set), then
 // scopes and resources
 int run_size_tail(Engine* e, const SizeKernelArgs& a, hipStream_t st) {
-  Engine::Timed tm{};
-  if (!a.kept_partials) {
-    e->prof_begin("size_span_kernel", st, tm);
-    launch_size_spans(a, st);
-    HIP_TRY(hipGetLastError());
-    e->prof_end(tm, st);
-  }
-  e->prof_begin("size_tail_kernel", st, tm);
-  launch_size_tail(a, st);
-  HIP_TRY(hipGetLastError());
-  e->prof_end(tm, st);
-  e->prof_begin("size_fix_kernel", st, tm);
-  launch_size_fix(a, st);
-  HIP_TRY(hipGetLastError());
-  e->prof_end(tm, st);
-  return 0;
+  if (!a.kept_partials)
+    if (const int rc = e->timed("size_span_kernel", st, [&] { launch_size_spans(a, st); })) return rc;
+  return run_size_scopes(e, a, st);
+}
+// what follows either spans pass: scopes and resources
+int run_size_scopes(Engine* e, const SizeKernelArgs& a, hipStream_t st) {
+  if (const int rc = e->timed("size_tail_kernel", st, [&] { launch_size_tail(a, st); })) return rc;
+  return e->timed("size_fix_kernel", st, [&] { launch_size_fix(a, st); });
 }
 
 int run_size(Engine* e, const ose_columns* c, const ose_outputs* o, uint32_t mask, uint32_t group_mode,

@@ -11,6 +11,19 @@ namespace ose {
 
 inline size_t up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
+// An offset cursor for the stage workspaces, which have no slack rule: take()
+// rounds the cursor up to `align`, hands that offset out and moves past the
+// part.  A layout function carves with it once; the bound and the pointers
+// both come from the offsets it returns.
+struct Carve {
+  size_t off = 0;
+  size_t take(size_t bytes, size_t align = 256) {
+    const size_t at = up(off, align);
+    off = at + bytes;
+    return at;
+  }
+};
+
 struct SlabPart {
   void** dst;                  // takes base + the part's offset
   size_t bytes;

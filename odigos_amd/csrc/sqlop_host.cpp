@@ -25,12 +25,7 @@ int run_sqlop(Engine* e, const ose_columns* c, const ose_outputs* o, hipStream_t
   a.resource = c->resource;
   a.res_sql_ok = c->res_sql_ok;
   a.sql_op = o->sql_op;
-  Engine::Timed tm{};
-  e->prof_begin("sqlop_kernel", st, tm);
-  launch_sqlop(a, st);
-  HIP_TRY(hipGetLastError());
-  e->prof_end(tm, st);
-  return 0;
+  return e->timed("sqlop_kernel", st, [&] { launch_sqlop(a, st); });
 }
 
 // SIZE after SQLOP / APPLY_SQLOP: what prepare_size does not ask for
@@ -41,23 +36,11 @@ int check_sqlop_size(const ose_columns* c, const ose_outputs* o) {
 
 // run_size_tail with sqlop_size_span_kernel as the spans pass
 int run_sqlop_size_tail(Engine* e, const SizeKernelArgs& a, const uint8_t* sql_op, hipStream_t st) {
-  Engine::Timed tm{};
   SqlSizeArgs sa{};
   sa.sz = a;
   sa.sql_op = sql_op;
-  e->prof_begin("sqlop_size_span_kernel", st, tm);
-  launch_sqlop_size_spans(sa, st);
-  HIP_TRY(hipGetLastError());
-  e->prof_end(tm, st);
-  e->prof_begin("size_tail_kernel", st, tm);
-  launch_size_tail(a, st);
-  HIP_TRY(hipGetLastError());
-  e->prof_end(tm, st);
-  e->prof_begin("size_fix_kernel", st, tm);
-  launch_size_fix(a, st);
-  HIP_TRY(hipGetLastError());
-  e->prof_end(tm, st);
-  return 0;
+  if (const int rc = e->timed("sqlop_size_span_kernel", st, [&] { launch_sqlop_size_spans(sa, st); })) return rc;
+  return run_size_scopes(e, a, st);
 }
 
 }  // namespace ose

@@ -227,6 +227,15 @@ def lib() -> C.CDLL:
         # host layer (odigos_amd/csrc/host.cpp)
         "osehost_last_error": (C.c_char_p, []),
         "osehost_sampling_chunks": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint32)]),
+        # the stage workspaces' layouts (no device): n_spans, [arena_bytes, nfa_words, refs,] off, bytes, cap, end
+        "osehost_sampling_layout": (C.c_uint32, [C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint32,
+                                                 C.POINTER(C.c_uint64)]),
+        "osehost_url_layout": (C.c_uint32, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(C.c_uint64),
+                                            C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint64),
+                                            C.POINTER(C.c_uint64)]),
+        # mask, defer, n_spans, n_scopes, n_resources, arena_bytes, url_words, out[4]
+        "osehost_stage_offsets": (None, [C.c_uint32, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
+                                         C.POINTER(C.c_uint64)]),
         "osehost_gbt_copy_times": (C.c_int, [_p, C.c_int, C.POINTER(C.c_double)]),
         "osehost_gbt_state": (C.c_int, [_p, C.POINTER(C.c_uint64), C.c_uint32]),
         "osehost_stream_copy": (C.c_int, [_p, _p, C.c_size_t, C.c_int, _p, C.POINTER(C.c_double)]),

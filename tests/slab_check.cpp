@@ -36,6 +36,25 @@ int main() {
   using namespace ose;
   if (up(0) != 0 || up(1) != 256 || up(256) != 256 || up(257) != 512 || up(17, 16) != 32) return bad("up");
 
+  // the stage workspaces' cursor: a part starts at the cursor rounded up to
+  // its alignment and the cursor moves past it, with no slack and no rounding
+  // behind the last part
+  {
+    Carve c;
+    if (c.take(0) != 0 || c.off != 0) return bad("Carve: a zero-byte part at 0");
+    if (c.take(40) != 0 || c.off != 40) return bad("Carve: the first part");
+    if (c.take(8, 8) != 40 || c.off != 48) return bad("Carve: already on the alignment");
+    if (c.take(3, 4) != 48 || c.off != 51) return bad("Carve: an odd size");
+    if (c.take(4, 4) != 52 || c.off != 56) return bad("Carve: rounded up to 4");
+    if (c.take(0) != 256 || c.off != 256) return bad("Carve: a zero-byte part moves the cursor to its alignment only");
+    if (c.take(256) != 256 || c.off != 512) return bad("Carve: exactly one unit");
+    if (c.take(257) != 512 || c.off != 769) return bad("Carve: one past a unit");
+    if (c.take(1, 1) != 769 || c.off != 770) return bad("Carve: alignment 1");
+    if (c.take(16) != 1024 || c.off != 1040) return bad("Carve: the default alignment is 256");
+    Carve d{256};   // a cursor that starts past a header
+    if (d.take(8 * 5) != 256 || d.take(4 * 5) != 512 || d.off != 532) return bad("Carve: started at 256");
+  }
+
   // bytes, kind (0 device-only, 1 sourced, 2 staged by the caller), and the
   // offset worked out by hand
   struct Row { size_t bytes; int kind; size_t at; };
