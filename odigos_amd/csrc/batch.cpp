@@ -24,10 +24,8 @@
 namespace ose {
 
 namespace {
-constexpr size_t kAlign = 256;
 constexpr size_t kPoolMax = 64;                    // pooled batches per engine
 constexpr size_t kPoolBytesMax = size_t(8) << 30;  // pinned bytes kept pooled per engine
-size_t up(size_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
 }  // namespace
 
 struct Batch {

@@ -13,6 +13,7 @@
 #include "../../include/odigos_amd.h"
 #include "config.hpp"
 #include "condattr_host.hpp"
+#include "slab.hpp"
 #include "timed_launch.hpp"
 
 namespace ose {
@@ -315,8 +316,6 @@ struct Engine {
 // the stream first and calls *tail before anything that reads keep
 int run_sampling(Engine* e, const ose_columns* c, const ose_outputs* o, uint32_t group_mode, const ose_rand* rnd,
                  hipStream_t st, Workspace* ws, std::function<int()>* tail = nullptr);
-// One part of a stage's workspace: byte offset from the stage's base, bytes.
-struct WsPart { size_t off, bytes; };
 // the trace stage's scratch past its 256 bytes of words (sampling_host.cpp)
 struct SamplingLayout {
   WsPart win_heads, win_base, wstatus, rec, key, k2, v2, k3, v3, hist, hoff, hstatus, long_runs, long_meta, long_pieces,
@@ -339,6 +338,17 @@ uint32_t layout_parts(const L& l, uint64_t* off, uint64_t* bytes, uint32_t cap, 
   return kParts;
 }
 size_t sampling_scratch_bytes(uint64_t n_spans);   // = sampling_layout(n_spans).end
+// The passes of the stable LSD radix sort on the keys' low `bits` bits (8-bit
+// digits: sort_hist, the scan of the 256 * n_tiles counts into hoff,
+// sort_scatter), ping-pong between kb[] / vb[].  `s`: n_spans, n_tiles, gate,
+// key, error and the scan words set; the first pass reads keys_in / vals_in
+// (null: s.key and the identity).  *keys / *vals: the last pass's output.
+struct TraceSortArgs;
+int radix_passes(TraceSortArgs s, uint32_t* const kb[2], uint32_t* const vb[2], uint32_t* hist, uint32_t* hoff,
+                 uint32_t htiles, int bits, const uint32_t* keys_in, const uint32_t* vals_in, hipStream_t st,
+                 const uint32_t** keys, const uint32_t** vals);
+// every column of `src` (device) whose pointer in `dst` is not NULL, copied there (engine.cpp)
+int download_columns(const ose_columns& src, const ose_columns* dst);
 // the attr_match bits the trace stage reads for this call (attr_host.cpp)
 int resolve_attr_match(Engine* e, const ose_columns* c, Workspace* ws, hipStream_t st, const uint64_t** out);
 // size stage scratch at workspace byte `off` (size_host.cpp)

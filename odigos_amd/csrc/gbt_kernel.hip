@@ -123,7 +123,7 @@ __device__ void gbt_put(const GbtArgs& a, uint64_t hi, uint64_t lo, uint64_t seq
     }
     if ((st & 3u) != 2u) {
       if (++spins > (1u << 20)) {
-        atomicOr(a.error, 1u);
+        atomicOr(a.error, kGbtErrSpin);
         return;
       }
       __builtin_amdgcn_s_sleep(1);
@@ -136,7 +136,7 @@ __device__ void gbt_put(const GbtArgs& a, uint64_t hi, uint64_t lo, uint64_t seq
     }
     h = (h + 1) & a.table_mask;
     if (++probes > a.table_mask) {
-      atomicOr(a.error, 4u);
+      atomicOr(a.error, kGbtErrProbe);
       return;
     }
   }
@@ -169,7 +169,7 @@ __device__ uint64_t gbt_lookup(const GbtArgs& a, uint64_t hi, uint64_t lo, uint3
     }
     if ((st & 3u) != 2u) {   // another lane is publishing or reclaiming this slot
       if (++spins > (1u << 20)) {
-        atomicOr(a.error, 1u);
+        atomicOr(a.error, kGbtErrSpin);
         return ~0ull;
       }
       __builtin_amdgcn_s_sleep(1);
@@ -179,7 +179,7 @@ __device__ uint64_t gbt_lookup(const GbtArgs& a, uint64_t hi, uint64_t lo, uint3
         __hip_atomic_load(&s->lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != lo) {
       h = (h + 1) & a.table_mask;   // another id (live or a tombstone)
       if (++probes > a.table_mask) {
-        atomicOr(a.error, 4u);
+        atomicOr(a.error, kGbtErrProbe);
         return ~0ull;
       }
       continue;
@@ -275,7 +275,7 @@ __global__ __launch_bounds__(kGbtThreads) void gbt_creator_kernel(GbtArgs a) {
 // (OTLP mode: blocks and header blocks, summed in 64 bits)
 template <bool kOtlp = false>
 __device__ __forceinline__ bool gbt_batch_refused(const GbtArgs& a) {
-  if constexpr (kOtlp) return a.otlp.total64[0] > a.arena_room || (a.error[0] & 16u);   // 16: a header not walked
+  if constexpr (kOtlp) return a.otlp.total64[0] > a.arena_room || (a.error[0] & kGbtErrHeader);
   return (uint64_t)a.totals[1] > a.arena_room;
 }
 
@@ -284,7 +284,7 @@ template <bool kOtlp>
 __global__ __launch_bounds__(kGbtThreads) void gbt_assign_kernel(GbtArgs a) {
   const uint64_t i = (uint64_t)blockIdx.x * kGbtThreads + threadIdx.x;
   if (gbt_batch_refused<kOtlp>(a)) {
-    if (i == 0) atomicOr(a.error, 8u);
+    if (i == 0) atomicOr(a.error, kGbtErrRefused);
     return;
   }
   if (i >= a.n || !a.flag[i]) return;
@@ -535,7 +535,7 @@ __global__ __launch_bounds__(kGbtThreads) void gbt_hdr_len_kernel(GbtArgs a) {
   const bool ok = gbt_hdr_fields<false>(a, (uint32_t)rr, (uint32_t)rr + (uint32_t)(rr >> 32), &hr, nullptr) &&
                   gbt_hdr_fields<false>(a, (uint32_t)sr, (uint32_t)sr + (uint32_t)(sr >> 32), &hs, nullptr);
   if (!ok) {
-    atomicOr(a.error, 16u);
+    atomicOr(a.error, kGbtErrHeader);
     hr = hs = 0;
   }
   a.otlp.hres[s] = hr;
@@ -587,7 +587,7 @@ __global__ __launch_bounds__(kGbtThreads) void gbt_frag_hdr_kernel(GbtArgs a, ui
       r.skip(wt);
     }
   }
-  if (r.bad) atomicOr(a.error, 16u);
+  if (r.bad) atomicOr(a.error, kGbtErrHeader);
   a.otlp.out_hdr[f] = nh > 1 ? kOtlpScopeMulti : hdr;
   a.otlp.out_schema[f] = schema;
 }

@@ -924,6 +924,11 @@ struct GbtSlot {              // trace id -> creation number (32 B, generation-t
                               // while add number `add` is numbering a new trace for it
 };
 constexpr uint64_t kGbtUnset = 0xFFFFFFFF00000000ull;
+// GbtArgs::error bits
+constexpr uint32_t kGbtErrSpin = 1;      // a slot stayed busy past the spin limit
+constexpr uint32_t kGbtErrProbe = 4;     // a table probe overran the table
+constexpr uint32_t kGbtErrRefused = 8;   // the batch is refused: the arena ring is full
+constexpr uint32_t kGbtErrHeader = 16;   // a ResourceSpans / ScopeSpans header not walked
 struct GbtPool {              // spans waiting for release (ring of pool_cap)
   uint64_t* tid;              // {hi, lo}
   uint64_t *start, *end, *attr_match, *seq, *origin, *str_off;

@@ -1688,27 +1688,7 @@ int ose_otlp_download(const ose_otlp_batch* bb, const ose_columns* dst) {
   if (!bb || !dst) return fail(OSE_EINVAL, "NULL argument");
   const auto* b = reinterpret_cast<const OtlpBatchImpl*>(bb);
   if (int rc = bind_device(b->e)) return rc;
-  const ose_columns& c = b->cols;
-  const uint64_t n = c.n_spans, R = c.n_resources, S = c.n_scopes, K = c.n_attr_keys;
-  struct F { const void* src; void* dst; size_t bytes; };
-  const F fs[] = {
-      {c.arena, (void*)dst->arena, c.arena_bytes}, {c.trace_id, (void*)dst->trace_id, 16 * n},
-      {c.start_ns, (void*)dst->start_ns, 8 * n}, {c.end_ns, (void*)dst->end_ns, 8 * n},
-      {c.status, (void*)dst->status, n}, {c.kind, (void*)dst->kind, n}, {c.resource, (void*)dst->resource, 4 * n},
-      {c.scope, (void*)dst->scope, 4 * n}, {c.url_flags, (void*)dst->url_flags, n}, {c.path, (void*)dst->path, 8 * n},
-      {c.route, (void*)dst->route, 8 * n}, {c.span_size, (void*)dst->span_size, 4 * n},
-      {c.name_len, (void*)dst->name_len, 4 * n}, {c.attr_match, (void*)dst->attr_match, 8 * n * std::max<uint32_t>(1, c.attr_match_words)},
-      {c.res_svc, (void*)dst->res_svc, 4 * R}, {c.res_svc_str, (void*)dst->res_svc_str, 4 * R},
-      {c.res_url_ok, (void*)dst->res_url_ok, R}, {c.res_attrset, (void*)dst->res_attrset, 4 * R},
-      {c.res_size, (void*)dst->res_size, 4 * R}, {c.scope_size, (void*)dst->scope_size, 4 * S},
-      {c.scope_resource, (void*)dst->scope_resource, 4 * S}, {c.attr_type, (void*)dst->attr_type, K * n},
-      {c.attr_val, (void*)dst->attr_val, 8 * K * n},
-      {c.db_flags, (void*)dst->db_flags, n}, {c.db_query, (void*)dst->db_query, 8 * n},
-      {c.res_sql_ok, (void*)dst->res_sql_ok, R},
-  };
-  for (auto& f : fs)
-    if (f.src && f.dst && f.bytes) HIP_TRY(hipMemcpy(f.dst, f.src, f.bytes, hipMemcpyDefault));
-  return 0;
+  return download_columns(b->cols, dst);
 }
 
 const ose_columns* ose_otlp_columns(const ose_otlp_batch* bb) {

@@ -416,6 +416,43 @@ int Workspace::reserve_fold(uint64_t n_spans) {
   return 0;
 }
 
+int radix_passes(TraceSortArgs s, uint32_t* const kb[2], uint32_t* const vb[2], uint32_t* hist, uint32_t* hoff,
+                 uint32_t htiles, int bits, const uint32_t* keys_in, const uint32_t* vals_in, hipStream_t st,
+                 const uint32_t** keys, const uint32_t** vals) {
+  s.scan_status_n = htiles;
+  int pass = 0;
+  for (int shift = 0; shift < bits; shift += 8, pass++) {
+    s.shift = (uint32_t)shift;
+    s.keys_in = keys_in;
+    s.vals_in = vals_in;
+    s.keys_out = kb[pass & 1];
+    s.vals_out = vb[pass & 1];
+    s.hist = hist;
+    launch_sort_hist(s, st);
+    HIP_TRY(hipGetLastError());
+    ScanArgs sa{};
+    sa.n = 256ull * s.n_tiles;
+    sa.n_tiles = htiles;
+    sa.gate = s.gate;
+    sa.in = hist;
+    sa.out = hoff;
+    sa.counter = s.scan_counter;
+    sa.status = s.scan_status;
+    sa.error = s.error;
+    launch_scan_u32(sa, st);
+    HIP_TRY(hipGetLastError());
+    TraceSortArgs s2 = s;
+    s2.hist = hoff;
+    launch_sort_scatter(s2, st);
+    HIP_TRY(hipGetLastError());
+    keys_in = kb[pass & 1];
+    vals_in = vb[pass & 1];
+  }
+  *keys = keys_in;
+  *vals = vals_in;
+  return 0;
+}
+
 int local_service_ids(Engine* e, const ose_columns* c, Workspace* ws, hipStream_t st, uint32_t chunk,
                       const uint32_t** out);
 
@@ -673,44 +710,14 @@ int run_sampling_pass(Engine* e, const ose_columns* c, const ose_outputs* o, uin
     // (the run-list kernel already put every run head in the exact table)
     launch_trace_key(s, st);
     HIP_TRY(hipGetLastError());
+    s.scan_counter = misc + 4;
+    s.scan_status = hstatus;
     int bits = 1;
     while (bits < 32 && (n - 1) >> bits) bits++;
-    const uint32_t* kin = nullptr;
-    const uint32_t* vin = nullptr;
-    uint32_t* kbuf[2] = {k2, k3};
-    uint32_t* vbuf[2] = {v2, v3};
-    int pass = 0;
-    for (int shift = 0; shift < bits; shift += 8, pass++) {
-      s.shift = (uint32_t)shift;
-      s.keys_in = kin;
-      s.vals_in = vin;
-      s.keys_out = kbuf[pass & 1];
-      s.vals_out = vbuf[pass & 1];
-      s.hist = hist;
-      s.scan_counter = misc + 4;
-      s.scan_status = hstatus;
-      s.scan_status_n = htiles;
-      launch_sort_hist(s, st);
-      HIP_TRY(hipGetLastError());
-      ScanArgs sa{};
-      sa.n = 256 * T;
-      sa.n_tiles = htiles;
-      sa.popcount = 0;
-      sa.gate = overflow;
-      sa.in = hist;
-      sa.out = hoff;
-      sa.counter = misc + 4;
-      sa.status = hstatus;
-      sa.error = err;
-      launch_scan_u32(sa, st);
-      HIP_TRY(hipGetLastError());
-      TraceSortArgs s2 = s;
-      s2.hist = hoff;
-      launch_sort_scatter(s2, st);
-      HIP_TRY(hipGetLastError());
-      kin = kbuf[pass & 1];
-      vin = vbuf[pass & 1];
-    }
+    const uint32_t *kin = nullptr, *vin = nullptr;   // the first pass reads `key` and the identity
+    uint32_t* const kbuf[2] = {k2, k3};
+    uint32_t* const vbuf[2] = {v2, v3};
+    if (int sr = radix_passes(s, kbuf, vbuf, hist, hoff, htiles, bits, nullptr, nullptr, st, &kin, &vin)) return sr;
     TraceKernelArgs b = a;
     b.dup = overflow;   // perm-mode evaluation is gated on this word
     b.mode = kTracePerm;

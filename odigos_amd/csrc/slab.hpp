@@ -23,6 +23,8 @@ struct Carve {
     return at;
   }
 };
+// One part of a carved layout: byte offset from the layout's base, bytes.
+struct WsPart { size_t off, bytes; };
 
 struct SlabPart {
   void** dst;                  // takes base + the part's offset

@@ -238,6 +238,10 @@ def lib() -> C.CDLL:
                                          C.POINTER(C.c_uint64)]),
         "osehost_gbt_copy_times": (C.c_int, [_p, C.c_int, C.POINTER(C.c_double)]),
         "osehost_gbt_state": (C.c_int, [_p, C.POINTER(C.c_uint64), C.c_uint32]),
+        # the store's layouts (no device): which, n, n_attrsets, n_scopes, n_resources, workers, otlp, off, bytes, cap, end
+        "osehost_gbt_layout": (C.c_uint32, [C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int,
+                                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint32,
+                                            C.POINTER(C.c_uint64)]),
         "osehost_stream_copy": (C.c_int, [_p, _p, C.c_size_t, C.c_int, _p, C.POINTER(C.c_double)]),
         "osehost_xgroup_create": (C.c_int, [C.c_int, C.POINTER(_p)]),
         "osehost_owner_last_general": (C.c_uint32, [_p]),

@@ -1,11 +1,13 @@
 // Host check of slab.hpp's carver on fake buffers: every part at the offset
 // the rule gives (256-byte starts, 16 bytes of slack behind each part, zero-byte
-// parts included), total and inputs, the staging copies, a failing need().
-// Run by test_slab.py.
+// parts included), total and inputs, the staging copies, a failing need();
+// and the byte offsets of the groupbytrace store's control words
+// (gbt_layout.hpp, HIP-free like slab.hpp).  Run by test_slab.py.
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 
+#include "../odigos_amd/csrc/gbt_layout.hpp"
 #include "../odigos_amd/csrc/slab.hpp"
 
 namespace {
@@ -53,6 +55,21 @@ int main() {
     if (c.take(16) != 1024 || c.off != 1040) return bad("Carve: the default alignment is 256");
     Carve d{256};   // a cursor that starts past a header
     if (d.take(8 * 5) != 256 || d.take(4 * 5) != 512 || d.off != 532) return bad("Carve: started at 256");
+  }
+
+  // the groupbytrace store's control words (gbt_layout.hpp), where gbt_kernel.hip
+  // and the scan and sort kernels have always been handed them
+  {
+    GbtWords w;
+    const uint8_t* base = reinterpret_cast<const uint8_t*>(&w);
+    const void* at[] = {&w.error, &w.totals[0], &w.totals[1], &w.worker_total, &w.scan_counter, &w.sort_gate,
+                        &w.hdr_total, &w.total64, &w.status[0]};
+    const size_t want[] = {0, 4, 8, 12, 16, 32, 36, 40, 64};
+    for (size_t k = 0; k < 9; k++)
+      if (static_cast<const uint8_t*>(at[k]) != base + want[k]) return bad("GbtWords: a member's offset");
+    if (kGbtWordsError != 4 || kGbtWordsCount != 8 || kGbtWordsTotals != 12 || kGbtWordsScans != 16 ||
+        kGbtWordsAll != 48 || kGbtWordsOtlp != 12)
+      return bad("GbtWords: a cleared or read-back prefix");
   }
 
   // bytes, kind (0 device-only, 1 sourced, 2 staged by the caller), and the

@@ -2,7 +2,8 @@
 OTLP decoder, the GPU encoder and the groupbytrace store is laid out by, and
 the cursor the stage workspaces are laid out by: tests/slab_check.cpp, a plain
 host program, checks offsets, sizes, staging copies and a failing need() on
-fake buffers.  tests/timed_check.cpp, another, drives the timed launch of the
+fake buffers, and the offsets of the store's control words (GbtWords,
+gbt_layout.hpp).  tests/timed_check.cpp, another, drives the timed launch of the
 stage hosts (timed_launch.hpp) against a fake event pool."""
 import subprocess
 from pathlib import Path
