@@ -460,7 +460,22 @@ int ose_engine_attr_key(const ose_engine* eng, uint32_t k, const char** key, uin
  *                          list lengths for ose_engine_path_counts (counts[3],
  *                          counts[4]) and ose_engine_url_nfa_groups.  Off by
  *                          default: nothing extra is queued.
- * and one test and measurement seam:
+ *                          (A call planned in slices, below, reports the
+ *                          sums over its slices.)
+ * and test and measurement seams:
+ *   "url_tail_slices"      value K, 0 to 8 (the one option whose value is a
+ *                          number): SAMPLE | TEMPLATE | TEMPLATE_REFS | SIZE
+ *                          calls by trace id (no SQLOP size, no NFA route)
+ *                          plan their groups in K slices on the side
+ *                          stream(s) and run each slice's spans pass on the
+ *                          caller's stream once that slice is planned; it
+ *                          also forks such a call at any span count >= 1.
+ *                          0 (the default): the engine's own rule, which
+ *                          leaves small batches unsliced and unforked.
+ *                          Results do not depend on K.
+ *   "url_tail_form"        value 0 to 2: the slices' form, 1 in order on one
+ *                          side stream, 2 staggered over two; 0 (the
+ *                          default): the rule's form.
  *   "url_regex_nfa"        the odigosurltemplate tables are built again with
  *                          every user regexp as an NFA program and TEMPLATE
  *                          takes the NFA route, so a config whose regexps

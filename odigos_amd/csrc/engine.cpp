@@ -67,7 +67,9 @@ Workspace::~Workspace() {
   for (void* f : fold)
     if (f) (void)hipFree(f);
   if (dup_host) (void)hipHostFree(dup_host);
-  for (hipEvent_t ev : {pending, dup_ready, fork, join, join2})
+  for (hipEvent_t ev : {pending, dup_ready, fork, join, join2, fork2})
+    if (ev) (void)hipEventDestroy(ev);
+  for (hipEvent_t ev : slice_ev)
     if (ev) (void)hipEventDestroy(ev);
 }
 
@@ -315,20 +317,40 @@ struct UrlFork {
     const hipError_t jw = je == hipSuccess ? hipStreamWaitEvent(st, ev, 0) : je;
     if (jw != hipSuccess) {   // cannot order the streams: wait for the URL work on the host
       (void)hipStreamSynchronize(ust);
+      if (ust2) (void)hipStreamSynchronize(ust2);
       if (!rc) rc = fail(OSE_EDEVICE, std::string("URL stream join: ") + hipGetErrorString(jw));
     }
   }
+  // The plan in K slices (kernels.hpp UrlSlices): an event per slice, and for
+  // the staggered form a second side stream and the event it starts behind.
+  // Returns the slices the call can have (1 when an event is missing; a
+  // staggered call without its second stream runs its slices in order).
+  hipStream_t ust2 = nullptr;
+  uint32_t open_slices(uint32_t k, uint32_t form) {
+    static_assert(sizeof(ws->slice_ev) / sizeof(ws->slice_ev[0]) == kUrlMaxSlices, "an event per slice");
+    if (k > kUrlMaxSlices) k = kUrlMaxSlices;
+    for (uint32_t s = 0; s < k; s++)
+      if (!ws->slice_ev[s] && hipEventCreateWithFlags(&ws->slice_ev[s], hipEventDisableTiming) != hipSuccess) return 1;
+    if (form == kUrlStaggered && k > 1) {
+      if (!ws->fork2) (void)hipEventCreateWithFlags(&ws->fork2, hipEventDisableTiming);
+      if (ws->fork2) ust2 = e->take_stream();
+    }
+    return k;
+  }
   void close() {
     if (ust) e->give_stream(ust);
-    ust = nullptr;
+    if (ust2) e->give_stream(ust2);
+    ust = ust2 = nullptr;
   }
 };
 
 // TEMPLATE and SIZE in one call: the spans pass rides in url_copy_kernel (one
 // walk over the spans)
-void fuse_size_into_copy(UrlKernelArgs& ua, SizeKernelArgs& sa, Workspace* ws, size_t size_off, const ose_columns* c) {
+// (S: the call's slices, each with a grid and a range of the partials of its own)
+void fuse_size_into_copy(UrlKernelArgs& ua, SizeKernelArgs& sa, Workspace* ws, size_t size_off, const ose_columns* c,
+                         const UrlSlices* S = nullptr) {
   sa.kept_partials = size_partials_of(ws, size_off, c->n_scopes, c->n_resources);
-  sa.n_kept_partials = url_copy_blocks(ua.n_groups);
+  sa.n_kept_partials = S ? S->part[S->k] : url_copy_blocks(ua.n_groups);
   ua.fuse_size = 1;
   ua.size_partials = const_cast<uint32_t*>(sa.kept_partials);
   ua.sz = sa;
@@ -425,7 +447,16 @@ int run_stages(Engine* e, const ose_columns* c, const ose_outputs* o, uint32_t m
   // (a small batch's kernels are launch-bound: a fork only adds two events
   // and a stream hand-off to each call of a request-sized batch)
   constexpr uint64_t kForkSpans = 1u << 20;
-  if (!one_stream && !rc && defer && n >= kForkSpans) fork.open();
+  // the refs form with the fused spans pass, the one that can run in slices
+  // (below); "url_tail_slices" forces the fork for it at any span count
+  const bool refs_fused = tmpl && (mask & OSE_STAGE_TEMPLATE_REFS) && (mask & OSE_STAGE_SIZE) && fused_size_ok;
+  const uint32_t forced_k = e->url_tail_slices_opt.load(std::memory_order_relaxed);
+  const uint32_t plan_groups = (uint32_t)((n + kUrlGroup - 1) / kUrlGroup);
+  // (not on the NFA route: no url_plan_kernel)
+  const uint32_t want_slices = refs_fused && !e->url_words() ? (forced_k ? forced_k : url_tail_slices(plan_groups)) : 1u;
+  const bool forks = !one_stream && !rc && defer && (n >= kForkSpans || (forced_k && refs_fused && !e->url_words()));
+  if (forks && want_slices > 1) rc = clear_url_slice_words(e, c, ws, so.url_off, st);
+  if (forks && !rc) fork.open();
   ws->beside_url = fork.ust && tmpl;
   // refs form with the fused spans pass: the copy / size launches need only
   // what url_plan_kernel and url_plan_slow_kernel wrote, so the join event is
@@ -434,7 +465,7 @@ int run_stages(Engine* e, const ose_columns* c, const ose_outputs* o, uint32_t m
   // stream is joined a second time at the end of the call
 #ifndef OSE_URL_JOIN_LATE
   // (not with sql_size: its spans pass reads the refs url_emit_slow_kernel writes)
-  fork.early_join = fork.ust && tmpl && (mask & OSE_STAGE_TEMPLATE_REFS) && (mask & OSE_STAGE_SIZE) && fused_size_ok;
+  fork.early_join = fork.ust && refs_fused;
 #endif
   // the plan grid beside the trace stage: 16x the resident workgroups
   // (C4 7.80 -> 7.62 ms, C5 3.49 -> 3.26; 4x: 7.88 / 3.27; alone, C2, the
@@ -448,12 +479,24 @@ int run_stages(Engine* e, const ose_columns* c, const ose_outputs* o, uint32_t m
   // 3.92 (4x) -> 3.82 (8x) -> 3.80 ms (16x, the multiplier this rule gives
   // it), C2 0.531 -> 0.520 (2x, its rule) -> 0.542 (4x) -> 0.935 (8x) -> 1.90
   // (16x) (profiles/r6s_plan_grid_serial_ab.txt)
-  const uint32_t plan_groups = (uint32_t)((n + kUrlGroup - 1) / kUrlGroup);
   UrlRun ur;
   ur.ws_off = so.url_off;
   ur.refs = (mask & OSE_STAGE_TEMPLATE_REFS) != 0;
   ur.grid_mult = url_plan_grid_mult(plan_groups, fork.ust != nullptr);
   ur.planned = fork.early_join ? ws->join : nullptr;
+  // ... and in slices (kernels.hpp UrlSlices): the spans pass of a slice needs
+  // only that slice's plan and the final keep bytes, which the trace stage
+  // has written long before the plan ends, so it runs on the caller's stream
+  // slice by slice beside the planning of the later slices; only the last
+  // slice's pass is left behind the plan.
+  const uint32_t form_opt = e->url_tail_form_opt.load(std::memory_order_relaxed);
+  const uint32_t form = form_opt ? form_opt - 1 : kUrlTailForm;
+  const uint32_t slices = fork.early_join && want_slices > 1 ? fork.open_slices(want_slices, form) : 1u;
+  ur.slices = slices;
+  ur.form = form;
+  ur.slice_ev = ws->slice_ev;
+  ur.st2 = fork.ust2;
+  ur.fork2 = ws->fork2;
   if (fork.ust && tmpl) {
     rc = run_url(e, c, o, fork.ust, ws, ur, &ua);
     // (an error before the record leaves the join to the usual place)
@@ -470,8 +513,11 @@ int run_stages(Engine* e, const ose_columns* c, const ose_outputs* o, uint32_t m
     const int trc = sample_tail();   // always drained: the host event wait must not be skipped
     if (!rc) rc = trc;
   }
-  // join: everything below runs on the caller's stream after both
-  if (fork.ust) fork.join(ws->join, fork.join_recorded, rc);
+  // join: everything below runs on the caller's stream after both (a sliced
+  // call joins slice by slice, below)
+  const bool sliced = slices > 1 && fork.join_recorded;
+  if (fork.ust2 && !sliced) (void)hipStreamSynchronize(fork.ust2);   // run_url failed between the slices
+  if (fork.ust && !sliced) fork.join(ws->join, fork.join_recorded, rc);
   // odigossqldboperationprocessor (orderHint 150): after odigosurltemplate,
   // before odigostrafficmetrics; it reads nothing the earlier stages write
   if (!rc && (mask & OSE_STAGE_SQLOP)) rc = run_sqlop(e, c, o, st);
@@ -480,7 +526,17 @@ int run_stages(Engine* e, const ose_columns* c, const ose_outputs* o, uint32_t m
   SizeKernelArgs sa{};
   bool size_on = false;
   if (!rc && (mask & OSE_STAGE_SIZE)) rc = prepare_size(e, c, o, mask, group_mode, rnd, st, ws, so.size_off, sa, size_on);
-  if (!rc && tmpl) {
+  if (sliced) {
+    // (the scope-sum clear of prepare_size thereby runs between the trace
+    // stage and the first slice's pass, off the step's tail)
+    const UrlSlices S = url_slices(ua.n_groups, slices, form);
+    if (!rc && size_on && n > 0) fuse_size_into_copy(ua, sa, ws, so.size_off, c, &S);
+    for (uint32_t s = 0; s < S.k; s++) {
+      if (S.g[s] == S.g[s + 1]) continue;
+      fork.join(ws->slice_ev[s], true, rc);   // every slice is waited for, whatever rc holds
+      if (!rc) rc = run_url_back_slice(e, ua, S, s, st);
+    }
+  } else if (!rc && tmpl) {
     if (size_on && n > 0 && fused_size_ok) fuse_size_into_copy(ua, sa, ws, so.size_off, c);
     rc = run_url_back(e, ua, st);
   }
@@ -710,6 +766,17 @@ int ose_engine_set_option(ose_engine* eng, const char* name, int64_t value) {
       {"otlp_condattr", Engine::kOptOtlpCondattr},
       {"url_regex_nfa", Engine::kOptUrlRegexNfa},
   };
+  // the two options that carry a number (engine_internal.hpp url_tail_slices_opt)
+  if (strcmp(name, "url_tail_slices") == 0) {
+    if (value < 0 || value > (int64_t)kUrlMaxSlices) return fail(OSE_EINVAL, "engine option url_tail_slices: 0 to 8");
+    e->url_tail_slices_opt.store((uint32_t)value);
+    return 0;
+  }
+  if (strcmp(name, "url_tail_form") == 0) {
+    if (value < 0 || value > 2) return fail(OSE_EINVAL, "engine option url_tail_form: 0 (the rule), 1 in order, 2 staggered");
+    e->url_tail_form_opt.store((uint32_t)value);
+    return 0;
+  }
   for (const auto& o : kOpts) {
     if (strcmp(name, o.name) != 0) continue;
     if (o.bit == Engine::kOptOtlpSqlop && !e->has_sqlop)

@@ -142,6 +142,10 @@ struct Workspace {
   // SAMPLE + TEMPLATE: the URL planning kernels run on a second stream
   // beside the trace stage (run_stages): fork and join events
   hipEvent_t fork = nullptr, join = nullptr, join2 = nullptr;
+  // ... planned in slices (kernels.hpp UrlSlices): one event per slice, and
+  // the staggered form's second side stream starts behind fork2
+  hipEvent_t slice_ev[8] = {};
+  hipEvent_t fork2 = nullptr;
   bool beside_url = false;   // this call's trace stage runs beside the forked URL planning
   Workspace() = default;
   Workspace(const Workspace&) = delete;
@@ -197,6 +201,11 @@ struct Engine {
   };
   std::atomic<uint32_t> options{0};
   bool option(uint32_t o) const { return (options.load(std::memory_order_relaxed) & o) != 0; }
+  // "url_tail_slices" (a test and measurement seam): the slices K of the
+  // forked refs form's plan and spans pass, forced (and the fork with it, at
+  // any span count); 0: url_tail_slices()'s rule.  "url_tail_form": their
+  // form + 1 (kernels.hpp kUrlInOrder / kUrlStaggered); 0: the rule's
+  std::atomic<uint32_t> url_tail_slices_opt{0}, url_tail_form_opt{0};
   bool url_needs_resource = false;
   int64_t inverse = 1;
   uint32_t max_name = 5;
@@ -358,6 +367,7 @@ struct SizeKernelArgs;
 int prepare_size(Engine* e, const ose_columns* c, const ose_outputs* o, uint32_t mask, uint32_t group_mode,
                  const ose_rand* rnd, hipStream_t st, Workspace* ws, size_t off, SizeKernelArgs& a, bool& active);
 uint32_t* size_partials_of(Workspace* ws, size_t off, uint64_t n_scopes, uint64_t n_resources);
+uint32_t size_partials_cap();   // the kept partials the size scratch reserves (any slicing of the spans pass)
 int run_size_tail(Engine* e, const SizeKernelArgs& a, hipStream_t st);
 int run_size_scopes(Engine* e, const SizeKernelArgs& a, hipStream_t st);   // size_tail_kernel, size_fix_kernel
 size_t size_scratch_bytes(uint64_t n_scopes, uint64_t n_resources);
@@ -403,17 +413,32 @@ struct UrlKernelArgs;
 // url_plan_grid_mult's.  planned: an event recorded on st behind
 // url_plan_slow_kernel, when every span's plan_len and url_out are written
 // (all the refs form's spans pass reads).
+// slices > 1 (kernels.hpp UrlSlices; the forked refs form only): the plan
+// launches go slice by slice, slice s's event slice_ev[s] is recorded behind
+// its url_plan_slow_kernel instead of `planned`, and in the staggered form
+// the odd slices run on st2, which st waits for before the scan.
 struct UrlRun {
   size_t ws_off = 0;
   bool refs = false;
   uint32_t grid_mult = 1;
   hipEvent_t planned = nullptr;
+  uint32_t slices = 1;
+  uint32_t form = 0;
+  hipEvent_t* slice_ev = nullptr;   // [slices]
+  hipStream_t st2 = nullptr;        // staggered form
+  hipEvent_t fork2 = nullptr;       // ... st2 starts behind st's clears
 };
+struct UrlSlices;
 // the front (plan, plan_slow, scan, emit_slow); the arguments of the rest go
 // to *front, and run_url_back queues url_copy, fused with
 // odigostrafficmetrics' spans pass when front->fuse_size is set
 int run_url(Engine* e, const ose_columns* c, const ose_outputs* o, hipStream_t st, Workspace* ws, const UrlRun& r,
             UrlKernelArgs* front);
 int run_url_back(Engine* e, const UrlKernelArgs& a, hipStream_t st);
+// a sliced call: its count words cleared (on the caller's stream, before the
+// fork), the arguments of slice s's launches, and its spans pass
+int clear_url_slice_words(Engine* e, const ose_columns* c, Workspace* ws, size_t ws_off, hipStream_t st);
+UrlKernelArgs url_slice_args(const UrlKernelArgs& a, const UrlSlices& S, uint32_t s);
+int run_url_back_slice(Engine* e, const UrlKernelArgs& a, const UrlSlices& S, uint32_t s, hipStream_t st);
 
 }  // namespace ose

@@ -70,7 +70,11 @@ struct SizeKernelArgs {
 
 struct UrlKernelArgs {
   uint64_t n_spans;
-  uint32_t n_groups;           // ceil(n_spans / kUrlGroup)
+  // The groups url_plan_kernel, url_plan_slow_kernel and the refs instance of
+  // url_copy_kernel work on in this launch: [0, n_groups), or one slice of it
+  // (UrlSlices; run_stages).  (Here, beside n_spans: one scalar load brings
+  // all the plan kernel's loop bounds.)
+  uint32_t g_begin, g_end;
   const uint8_t* arena;
   const uint8_t* url_flags;
   const uint8_t* kind;
@@ -91,6 +95,7 @@ struct UrlKernelArgs {
   uint64_t* group_scr;         // [n_groups] scratch offset of the group's image, ~0: slow group
   uint64_t* group_sum;         // [n_groups]
   uint64_t* group_base;        // [n_groups] exclusive prefix
+  uint32_t n_groups;           // ceil(n_spans / kUrlGroup)
   uint32_t n_scan_tiles;       // ceil(n_groups / kUrlScanTile)
   uint32_t* scan_counter;      // zeroed before launch
   uint64_t* scan_status;       // [n_scan_tiles], zeroed before launch
@@ -128,6 +133,13 @@ struct UrlKernelArgs {
   uint32_t fuse_size;
   uint32_t* size_partials;
   SizeKernelArgs sz;
+  // A slice's launches ([g_begin, g_end) above) have its own unplanned list
+  // and count word (unplanned + g_begin, so the lists never overlap) and add
+  // the list lengths into *unplanned_total (null: not sliced); its spans pass
+  // runs copy_blocks workgroups (0: url_copy_blocks(n_groups)) and counts
+  // into size_partials[partial_off + block].
+  uint32_t copy_blocks, partial_off;
+  uint32_t* unplanned_total;
 };
 constexpr uint32_t kUrlCopyMaxBlocks = 65536;
 uint32_t url_copy_blocks(uint32_t n_groups);
@@ -167,6 +179,64 @@ inline uint32_t url_plan_grid_mult(uint32_t n_groups, bool forked = false) {
   const uint32_t m = n_groups / (kUrlMaxWaves * 19u);
   return m < 1 ? 1u : m > 16 ? 16u : m;
 }
+// The one-GPU forked refs form with the fused spans pass (run_stages) cuts
+// the batch's groups into K slices of consecutive groups: each slice is
+// planned by its own url_plan_kernel / url_plan_slow_kernel launches on the
+// side stream(s), and its spans pass (url_copy_kernel<true, true>) runs on the
+// caller's stream as soon as the slice is planned, beside the planning of the
+// later slices, instead of behind the whole plan.
+//   kUrlInOrder    equal slices, one after another on one side stream
+//   kUrlStaggered  slices alternating between two side streams, the first
+//                  half as long as the others, so a slice's ramp falls into
+//                  the drain of the slice before it
+enum : uint32_t { kUrlInOrder = 0, kUrlStaggered = 1 };
+constexpr uint32_t kUrlMaxSlices = 8;
+// (a first slice of 2/3 or 4/5 of the others measured the same as 1/2 at
+// K = 2, 6.69-6.70 ms on C4; with 4/5 the first slice's url_plan_slow_kernel
+// ends 0.4 ms late beside the other slice's plan, with 1/2 that is hidden)
+constexpr uint32_t kUrlStaggerNum = 1, kUrlStaggerDen = 2;
+struct UrlSlices {
+  uint32_t k;                          // slices (1: the unsliced call)
+  uint32_t g[kUrlMaxSlices + 1];       // slice s holds the groups [g[s], g[s + 1])
+  uint32_t part[kUrlMaxSlices + 1];    // ... and its spans pass counts into size_partials[part[s], part[s + 1])
+};
+// (the spans pass's grid over a slice: the unsliced grid's cap shared among
+// the slices, so the K grids together never count into more than
+// kUrlCopyMaxBlocks partials, which is what the size scratch reserves, and a
+// wave keeps the groups it has in the unsliced grid of a large batch)
+inline uint32_t url_slice_copy_blocks(uint32_t groups, uint32_t k) {
+  if (k <= 1) return url_copy_blocks(groups);
+  const uint32_t want = (groups + 7) / 8, cap = kUrlCopyMaxBlocks / k;
+  return groups == 0 ? 0u : want < cap ? want : cap;
+}
+inline UrlSlices url_slices(uint32_t n_groups, uint32_t k, uint32_t form) {
+  UrlSlices s{};
+  s.k = k < 1 ? 1u : k > kUrlMaxSlices ? kUrlMaxSlices : k;
+  // staggered: the first slice kUrlStaggerNum / kUrlStaggerDen of each other
+  // one (bounds rounded up: no slice is empty once there are K groups)
+  const uint64_t first = form == kUrlStaggered ? kUrlStaggerNum : 1, each = form == kUrlStaggered ? kUrlStaggerDen : 1;
+  const uint64_t d = first + (s.k - 1) * each;
+  for (uint32_t j = 1; j < s.k; j++) {
+    const uint64_t num = (uint64_t)n_groups * (first + (j - 1) * each);
+    s.g[j] = (uint32_t)((num + d - 1) / d);
+  }
+  s.g[s.k] = n_groups;
+  for (uint32_t j = 0; j < s.k; j++) s.part[j + 1] = s.part[j] + url_slice_copy_blocks(s.g[j + 1] - s.g[j], s.k);
+  return s;
+}
+// The slices of a batch of n_groups groups (1: unsliced) and their form
+// (profiles/tail_slices_ab.txt, one MI355X, C4).  Every url_plan_kernel
+// launch that starts behind another on one stream costs about 0.2 ms (the
+// grid drains and refills), more than a slice's spans pass saves: in order,
+// 100M spans run 6.82 (K = 1) -> 7.04 (2) -> 7.28 (3) -> 7.45 (4) -> 8.14 ms
+// (8).  Staggered, two slices start together and nothing drains before the
+// end: 6.69 (2) -> 6.81 (3) -> 6.88 (4) -> 6.92 (8); a third launch again
+// costs more than it saves.  Two staggered slices gain 0.13 ms at 100M spans,
+// 0.03 at 30M (one run each, inside the noise) and lose 0.05 at 10M and 0.04
+// at 3M, so the rule slices from 2^20 groups (67M spans) up.
+constexpr uint32_t kUrlTailForm = kUrlStaggered;
+constexpr uint32_t kUrlTailGroups = 1u << 20;
+inline uint32_t url_tail_slices(uint32_t n_groups) { return n_groups >= kUrlTailGroups ? 2u : 1u; }
 void launch_url_plan(const UrlKernelArgs& a, hipStream_t st);
 uint32_t url_plan_waves(const UrlKernelArgs& a);   // waves of the plan grid (scratch regions)
 // refs form: the image chunk size for an arena of `cap` bytes over `waves`

@@ -13,6 +13,7 @@ namespace ose {
 namespace {
 struct SizeLayout {
   size_t scope, parts, fix, partials, end;
+  uint32_t n_partials;   // kept partials reserved
 };
 SizeLayout size_layout(uint64_t n_scopes) {
   const uint64_t W = (std::max<uint64_t>(n_scopes, 1) + 63) / 64;
@@ -21,7 +22,11 @@ SizeLayout size_layout(uint64_t n_scopes) {
   L.parts = up(L.scope + 8 * std::max<uint64_t>(n_scopes, 1));
   L.fix = up(L.parts + 32 * W);
   L.partials = up(L.fix + 4 * W);
-  L.end = up(L.partials + 4ull * kUrlCopyMaxBlocks) + 256;
+  // the fused spans pass counts per workgroup: one grid of at most
+  // kUrlCopyMaxBlocks, or a sliced call's K grids, which share that cap
+  // (url_slice_copy_blocks), so no K counts into more
+  L.n_partials = kUrlCopyMaxBlocks;
+  L.end = up(L.partials + 4ull * L.n_partials) + 256;
   return L;
 }
 }  // namespace
@@ -105,6 +110,8 @@ uint32_t* size_partials_of(Workspace* ws, size_t off, uint64_t n_scopes, uint64_
   (void)n_resources;
   return reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(ws->dev) + off + size_layout(n_scopes).partials);
 }
+
+uint32_t size_partials_cap() { return size_layout(1).n_partials; }
 
 // the spans pass (unless url_copy_kernel ran it: a.kept_partials set), then
 // scopes and resources

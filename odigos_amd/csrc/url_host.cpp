@@ -209,6 +209,8 @@ UrlKernelArgs url_args(const Engine* e, const ose_columns* c, const ose_outputs*
   UrlKernelArgs a{};
   a.n_spans = n;
   a.n_groups = (uint32_t)((n + kUrlGroup - 1) / kUrlGroup);
+  a.g_begin = 0;
+  a.g_end = a.n_groups;
   a.arena = c->arena;
   a.url_flags = c->url_flags;
   a.kind = c->kind;
@@ -259,17 +261,49 @@ UrlKernelArgs url_args(const Engine* e, const ose_columns* c, const ose_outputs*
   return a;
 }
 
-// fill or plan, slow plan, (planned), scan, slow emit, and the path counts
-int queue_url_front(Engine* e, const UrlKernelArgs& a, hipStream_t st, hipEvent_t planned) {
+// a sliced call's words: [0] the sum of the slices' unplanned counts, [1 + s]
+// slice s's count: the upper half of the dbg part (the diagnostic clocks use
+// the lower)
+constexpr size_t kSliceWordBytes = 64;
+static_assert(4 * (1 + kUrlMaxSlices) <= kSliceWordBytes, "a count word per slice and their sum");
+uint32_t* url_slice_words(uint8_t* base, const UrlLayout& L) { return reinterpret_cast<uint32_t*>(base + L.dbg.off + 128); }
+
+// fill or plan, slow plan: of the batch, or of one slice of it (url_slice_args)
+int queue_url_plan(Engine* e, const UrlKernelArgs& a, hipStream_t st) {
   int rc;
   if (a.nfa) {   // every group listed as unplanned, then planned per lane
     if ((rc = e->timed("url_nfa_fill_kernel", st, [&] { launch_url_nfa_fill(a, st); }))) return rc;
-    if ((rc = e->timed("url_nfa_plan_kernel", st, [&] { launch_url_nfa_plan(a, st); }))) return rc;
-  } else {
-    if ((rc = e->timed("url_plan_kernel", st, [&] { launch_url_plan(a, st); }))) return rc;
-    if ((rc = e->timed("url_plan_slow_kernel", st, [&] { launch_url_plan_slow(a, st); }))) return rc;
+    return e->timed("url_nfa_plan_kernel", st, [&] { launch_url_nfa_plan(a, st); });
   }
-  if (planned) HIP_TRY(hipEventRecord(planned, st));
+  if ((rc = e->timed("url_plan_kernel", st, [&] { launch_url_plan(a, st); }))) return rc;
+  return e->timed("url_plan_slow_kernel", st, [&] { launch_url_plan_slow(a, st); });
+}
+
+// The plan slice by slice, each slice's event recorded behind its slow plan
+// (its spans pass waits for that event alone); staggered: the odd slices on
+// r.st2, which starts behind st's clears and which st waits for at the end,
+// so what follows on st comes after every slice.
+int queue_url_slices(Engine* e, const UrlKernelArgs& a, const UrlSlices& S, const UrlRun& r, hipStream_t st) {
+  const bool two = r.form == kUrlStaggered && r.st2 && r.fork2;
+  if (two) {
+    HIP_TRY(hipEventRecord(r.fork2, st));
+    HIP_TRY(hipStreamWaitEvent(r.st2, r.fork2, 0));
+  }
+  hipEvent_t last2 = nullptr;
+  for (uint32_t s = 0; s < S.k; s++) {
+    if (S.g[s] == S.g[s + 1]) continue;   // fewer groups than slices
+    hipStream_t ss = two && (s & 1) ? r.st2 : st;
+    if (const int rc = queue_url_plan(e, url_slice_args(a, S, s), ss)) return rc;
+    HIP_TRY(hipEventRecord(r.slice_ev[s], ss));
+    if (ss != st) last2 = r.slice_ev[s];
+  }
+  if (last2) HIP_TRY(hipStreamWaitEvent(st, last2, 0));
+  return 0;
+}
+
+// behind the plan: scan, slow emit, and the path counts
+int queue_url_rest(Engine* e, const UrlKernelArgs& a, hipStream_t st) {
+  int rc;
   if ((rc = e->timed("url_scan_kernel", st, [&] { launch_url_scan(a, st); }))) return rc;
   // the groups url_plan_kernel did not assemble, written at their scanned
   // bases: nothing here reads SAMPLE's keep bytes or url_copy_kernel's
@@ -283,7 +317,9 @@ int queue_url_front(Engine* e, const UrlKernelArgs& a, hipStream_t st, hipEvent_
   // "url_path_counts" (tests): which kernel took this call's groups, kept in
   // two spare words of the engine's path counters (ose_engine_path_counts)
   if ((e->options.load() & Engine::kOptUrlPathCounts) && e->path_count_dev) {
-    HIP_TRY(hipMemcpyAsync(e->path_count_dev + 2, a.unplanned_count, 4, hipMemcpyDeviceToDevice, st));
+    // (a sliced call: the slices' lists summed by their url_plan_slow_kernel launches)
+    const uint32_t* unplanned = a.unplanned_total ? a.unplanned_total : a.unplanned_count;
+    HIP_TRY(hipMemcpyAsync(e->path_count_dev + 2, unplanned, 4, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(e->path_count_dev + 3, a.slow_count, 4, hipMemcpyDeviceToDevice, st));
     // word 4: the groups the NFA route took (ose_engine_url_nfa_groups)
     if (a.nfa) HIP_TRY(hipMemcpyAsync(e->path_count_dev + 4, a.unplanned_count, 4, hipMemcpyDeviceToDevice, st));
@@ -337,9 +373,56 @@ int run_url(Engine* e, const ose_columns* c, const ose_outputs* o, hipStream_t s
     a.dbg = reinterpret_cast<uint64_t*>(base + L.dbg.off);
     HIP_TRY(hipMemsetAsync(a.dbg, 0, 256, st));
   }
-  rc = queue_url_front(e, a, st, r.planned);
+  if (r.slices > 1 && r.refs && !a.nfa && r.slice_ev) {
+    // the slices' count words and their sum (cleared by clear_url_slice_words);
+    // one image chunk size for the plan waves of all slices together, so the
+    // arena's unused chunk tails stay under an eighth of it whatever K is
+    const UrlSlices S = url_slices(a.n_groups, r.slices, r.form);
+    a.unplanned_total = url_slice_words(base, L);
+    uint32_t waves = 0;
+    for (uint32_t s = 0; s < S.k; s++)
+      if (S.g[s] < S.g[s + 1]) waves += url_plan_waves(url_slice_args(a, S, s));
+    a.plan_waves = waves;
+    a.refs_chunk = url_refs_chunk(o->tmpl_arena_cap, waves);
+    *front = a;
+    rc = queue_url_slices(e, a, S, r, st);
+  } else {
+    rc = queue_url_plan(e, a, st);
+    if (!rc && r.planned) HIP_TRY(hipEventRecord(r.planned, st));
+  }
+  if (!rc) rc = queue_url_rest(e, a, st);
   if (!rc) *front = a;
   return rc;
+}
+
+UrlKernelArgs url_slice_args(const UrlKernelArgs& a, const UrlSlices& S, uint32_t s) {
+  UrlKernelArgs x = a;
+  x.g_begin = S.g[s];
+  x.g_end = S.g[s + 1];
+  x.plan_grid_mult = url_plan_grid_mult(x.g_end - x.g_begin, true);   // a wave keeps its ~19 groups
+  x.unplanned = a.unplanned + x.g_begin;
+  x.unplanned_count = a.unplanned_total + 1 + s;
+  x.copy_blocks = S.part[s + 1] - S.part[s];
+  x.partial_off = S.part[s];
+  return x;
+}
+
+// The slices' count words cleared on the caller's stream ahead of the fork:
+// on the side stream the fill would be queued as the trace stage's grid
+// starts, where a fill was measured starved (285 us for these 64 bytes,
+// profiles/tail_slices_ab.txt), and the zeroed part of the layout has no
+// room for them.
+int clear_url_slice_words(Engine* e, const ose_columns* c, Workspace* ws, size_t ws_off, hipStream_t st) {
+  const UrlLayout L = url_layout(c->n_spans, c->arena_bytes, e->url_words(), true);
+  if (const int rc = ws->reserve(ws_off + L.end)) return rc;
+  HIP_TRY(hipMemsetAsync(url_slice_words(static_cast<uint8_t*>(ws->dev) + ws_off, L), 0, kSliceWordBytes, st));
+  return 0;
+}
+
+int run_url_back_slice(Engine* e, const UrlKernelArgs& a, const UrlSlices& S, uint32_t s, hipStream_t st) {
+  if (S.g[s] == S.g[s + 1] || !a.fuse_size) return 0;
+  const UrlKernelArgs x = url_slice_args(a, S, s);
+  return e->timed("url_copy_kernel", st, [&] { launch_url_copy(x, st); });
 }
 
 int run_url_back(Engine* e, const UrlKernelArgs& a, hipStream_t st) {
@@ -362,6 +445,24 @@ extern "C" uint32_t osehost_url_layout(uint64_t n_spans, uint64_t arena_bytes, u
                                        uint64_t* bytes, uint32_t cap, uint64_t* end, uint64_t* workspace_bytes) {
   if (workspace_bytes) *workspace_bytes = url_workspace_bytes(n_spans, arena_bytes, nfa_words);
   return layout_parts(url_layout(n_spans, arena_bytes, nfa_words, refs != 0), off, bytes, cap, end);
+}
+
+// Diagnostic, no device: the slices of a sliced call (kernels.hpp url_slices),
+// K = 0: url_tail_slices()'s rule and form.  out[0] = the slices, out[1] = the
+// kept partials the size scratch reserves, out[2..11) the group bounds,
+// out[11..20) the partial offsets (entries past the slices' repeat the end).
+extern "C" void osehost_url_slices(uint32_t n_groups, uint32_t k, uint32_t form, uint32_t* out) {
+  if (k == 0) {
+    k = url_tail_slices(n_groups);
+    form = kUrlTailForm;
+  }
+  const UrlSlices S = url_slices(n_groups, k, form);
+  out[0] = S.k;
+  out[1] = size_partials_cap();
+  for (uint32_t j = 0; j <= kUrlMaxSlices; j++) {
+    out[2 + j] = S.g[j < S.k ? j : S.k];
+    out[3 + kUrlMaxSlices + j] = S.part[j < S.k ? j : S.k];
+  }
 }
 
 // FNV-1a of the odigosurltemplate device tables of an engine config, their

@@ -1553,8 +1553,8 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
     a.dbg = nullptr;
   }
   const uint32_t stride = wave_stride();
-  uint32_t g = wave_first_group();
-  if (g >= a.n_groups) return;
+  uint32_t g = a.g_begin + wave_first_group();   // this launch's groups: [g_begin, g_end)
+  if (g >= a.g_end) return;
   const bool tm = (kMode & kModeDiag) && a.dbg != nullptr;
   uint64_t t0 = 0, t_stage = 0, t_bm = 0, t_plan = 0, t_emit = 0, tt[3] = {0, 0, 0};
   const bool fused_cfg = sm.bn.ok && !(a.ablate & 2);
@@ -1587,7 +1587,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
     lds_u32* stage32 = (lds_u32*)stage;
     const uint64_t i = (uint64_t)g * kWave + lane;
     const uint32_t g2 = g + stride;
-    const bool more = g2 < a.n_groups;
+    const bool more = g2 < a.g_end;
     // in flight while this group is planned: the columns of the group after the next
     const bool np2 = more && plan_gate(nxt) == 2;
     nn = plan_cols(a, (uint64_t)(g2 + stride) * kWave + lane);
@@ -1925,20 +1925,23 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(kSize 
   const uint32_t stride = wave_stride();
   uint32_t kept = 0;
   const bool sz_on = kSize && !sizedev::size_batch_dropped(a.sz);
-  uint32_t g = wave_first_group();
-  if (kRefs && !sz_on) g = a.n_groups;   // a dropped batch: nothing to count
+  // the refs instance works on the launch's groups [g_begin, g_end) (a slice
+  // of the batch, run_stages) and counts into its own size_partials
+  const uint32_t g_end = kRefs ? a.g_end : a.n_groups;
+  uint32_t g = (kRefs ? a.g_begin : 0u) + wave_first_group();
+  if (kRefs && !sz_on) g = g_end;   // a dropped batch: nothing to count
   // the next group's columns are loaded while this group is worked on
   CopyCols An{0, 0, 0, ~0ull};
   sizedev::SpanCols xn{};
-  if (g < a.n_groups) {
+  if (g < g_end) {
     An = kRefs ? copy_len(a, g, lane) : copy_cols(a, g, lane);
     if (kSize && sz_on) xn = sizedev::size_span_load(a.sz, (uint64_t)g * kWave + lane, false);
   }
-  for (; g < a.n_groups; g += stride) {
+  for (; g < g_end; g += stride) {
     const uint64_t ia = (uint64_t)g * kWave + lane;
     const CopyCols A = An;
     const sizedev::SpanCols x0 = xn;
-    const bool more = g + stride < a.n_groups;
+    const bool more = g + stride < g_end;
     if (more) {
       An = kRefs ? copy_len(a, g + stride, lane) : copy_cols(a, g + stride, lane);
       if (kSize && sz_on) xn = sizedev::size_span_load(a.sz, (uint64_t)(g + stride) * kWave + lane, false);
@@ -1970,7 +1973,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(kSize 
     if (threadIdx.x == 0) {
       uint32_t t = 0;
       for (int w = 0; w < kWaves; w++) t += wk[w];
-      a.size_partials[blockIdx.x] = t;
+      a.size_partials[(kRefs ? a.partial_off : 0u) + blockIdx.x] = t;
     }
   }
 }
@@ -1994,7 +1997,9 @@ struct SlowPlanSmem {
 };
 __global__ __launch_bounds__(kWave) void url_plan_slow_kernel(UrlKernelArgs a) {
   __shared__ SlowPlanSmem sm;
-  const uint32_t count = *a.unplanned_count;
+  const uint32_t count = *a.unplanned_count;   // the list of the launch's groups [g_begin, g_end)
+  // (a sliced call: the lists' lengths summed for the url_path_counts witness)
+  if (a.unplanned_total && blockIdx.x == 0 && threadIdx.x == 0 && count) atomicAdd(a.unplanned_total, count);
   if (blockIdx.x >= count) return;
   const int lane = threadIdx.x;
   const uint64_t c0 = a.dbg ? clk() : 0;
@@ -2298,7 +2303,8 @@ static int url_mode(const UrlKernelArgs& a) {
   return (a.general ? kModeGeneral : 0) | ((OSE_DIAG && (a.ablate || a.dbg)) ? kModeDiag : 0);
 }
 template <int M>
-static uint32_t plan_blocks(const UrlKernelArgs& a) {
+static uint32_t plan_blocks(UrlKernelArgs a) {
+  a.n_groups = a.g_end - a.g_begin;   // the launch's groups: the batch's, or one slice's (url_slice_args)
   static const uint32_t res = resident_blocks(url_plan_kernel<M>, 0);
   // beside the trace stage (refs form: no per-wave scratch regions) the grid
   // is several times the resident one, so the dispatcher interleaves its
@@ -2348,7 +2354,7 @@ uint32_t url_copy_blocks(uint32_t n_groups) {
   return std::max<uint32_t>(1, std::min<uint32_t>(kUrlCopyMaxBlocks, (n_groups + 2 * kWaves - 1) / (2 * kWaves)));
 }
 void launch_url_copy(const UrlKernelArgs& a, hipStream_t st) {
-  const uint32_t blocks = url_copy_blocks(a.n_groups);
+  const uint32_t blocks = a.copy_blocks ? a.copy_blocks : url_copy_blocks(a.n_groups);
   if (a.refs) {   // the refs form: nothing to copy, only the fused spans pass
     if (a.fuse_size) hipLaunchKernelGGL((url_copy_kernel<true, true>), dim3(blocks), dim3(kThreads), 0, st, a);
   } else if (a.fuse_size) {
@@ -2368,7 +2374,7 @@ void launch_url_plan_slow(const UrlKernelArgs& a, hipStream_t st) {
       per_cu = 2;
     return (uint32_t)(cus * per_cu);
   }();
-  const uint32_t blocks = std::min<uint32_t>(cap, a.n_groups);
+  const uint32_t blocks = std::min<uint32_t>(cap, a.g_end - a.g_begin);
   if (blocks) hipLaunchKernelGGL(url_plan_slow_kernel, dim3(blocks), dim3(kWave), 0, st, a);
 }
 void launch_url_emit_slow(const UrlKernelArgs& a, hipStream_t st) {

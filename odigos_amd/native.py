@@ -236,6 +236,8 @@ def lib() -> C.CDLL:
         # mask, defer, n_spans, n_scopes, n_resources, arena_bytes, url_words, out[4]
         "osehost_stage_offsets": (None, [C.c_uint32, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
                                          C.POINTER(C.c_uint64)]),
+        # n_groups, K (0: the rule), form, out[20]: the slices of the forked refs form's plan and spans pass
+        "osehost_url_slices": (None, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
         "osehost_gbt_copy_times": (C.c_int, [_p, C.c_int, C.POINTER(C.c_double)]),
         "osehost_gbt_state": (C.c_int, [_p, C.POINTER(C.c_uint64), C.c_uint32]),
         # the store's layouts (no device): which, n, n_attrsets, n_scopes, n_resources, workers, otlp, off, bytes, cap, end
