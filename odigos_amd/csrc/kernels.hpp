@@ -511,7 +511,9 @@ void launch_shard_unpack(const UnpackArgs& a, hipStream_t st);
 // workgroup per bucket groups, orders and folds its traces in LDS.
 constexpr uint32_t kOwnerCap = 256;   // records one bucket holds (a fuller bucket: the general path)
 constexpr uint32_t kOwnerAvg = 80;    // records per bucket the host sizes the bucket count for
-constexpr uint32_t kOwnerSlotWords = 8;   // a bucket slot: hi, lo, min start, max end, {w4 | index << 32}, chunk 0's words, 0
+// a bucket slot, 64 bytes written and read as four uint4 (owner_bucket_kernel / owner_fold_kernel):
+// {hi, lo} | {min start, max end} | {w4 : 32, record index : 32, chunk 0's endpoint word} | {chunk 0's rule word, 0}
+constexpr uint32_t kOwnerSlotWords = 8;
 struct OwnerArgs {
   const uint8_t* recv;        // n records of x_rec_words(n_chunks) words, in (source rank, source order)
   uint64_t n;

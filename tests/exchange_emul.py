@@ -30,14 +30,29 @@ XDT = np.dtype([("hi", "<u8"), ("lo", "<u8"), ("m", "<u8"), ("e", "<u8"), ("w4",
 REC_BYTES = XDT.itemsize   # 56
 
 
+def xdt(chunks: int = 1) -> np.dtype:
+    """The record of a K-chunk config: chunk 0's words keep the one-chunk
+    names (ep, svcb), chunk k >= 1 has (ep<k>, svcb<k>)."""
+    extra = [(f"{f}{k}", "<u8") for k in range(1, chunks) for f in ("ep", "svcb")]
+    return np.dtype(XDT.descr + extra)
+
+
+def chunk_words(r: np.ndarray, chunks: int):
+    """(endpoint words, rule words) of structured records as [chunks, n] planes."""
+    ep = np.stack([r["ep" if k == 0 else f"ep{k}"] for k in range(chunks)])
+    sb = np.stack([r["svcb" if k == 0 else f"svcb{k}"] for k in range(chunks)])
+    return ep, sb
+
+
 class RuleLayout:
     """The device rule tables' bit layout (sampling_host.cpp build_sampling_tables):
     interned service ids, latency slot per service, service_name rule bit per
-    service, span_attribute bits after the service rules."""
+    service, span_attribute bits after the service rules.  ids: the engine's
+    interned services when cfg is one rule chunk of a longer list."""
 
-    def __init__(self, cfg: dict):
+    def __init__(self, cfg: dict, ids: dict | None = None):
         from tests.oracle_lib import intern_services
-        self.ids = intern_services(cfg)
+        self.ids = intern_services(cfg) if ids is None else ids
         self.nsvc = len(self.ids)
         self.slot = {}
         self.svc_bits = np.zeros(max(self.nsvc, 1), dtype=np.uint64)
@@ -102,9 +117,17 @@ def endpoint_bits(cfg: dict, res_svc_of_span, route_bytes) -> np.ndarray:
     return out
 
 
-def pack(tid: np.ndarray, start, end, status, svc, svc_str, ep, world: int, attr=None, *, cfg: dict):
-    """-> (records in bucket order [XDT], counts[world] (records), pack_pos[n])"""
+def pack(tid: np.ndarray, start, end, status, svc, svc_str, ep, world: int, attr=None, *, cfg: dict,
+         chunk_cfgs=None):
+    """-> (records in bucket order [XDT], counts[world] (records), pack_pos[n])
+
+    chunk_cfgs: the rule chunks of cfg as configs of their own (each chunk's
+    rules in level order).  The records are then xdt(K): cut and folded by
+    cfg's latency services, with chunk k's endpoint and rule words under chunk
+    k's own bit layout; ep is [K, n], chunk k's plane in chunk k's bits."""
     lay = RuleLayout(cfg)
+    chunks = [lay] if chunk_cfgs is None else [RuleLayout(c, lay.ids) for c in chunk_cfgs]
+    assert attr is None or len(chunks) == 1, "span_attribute bits: one-chunk configs only"
     n = len(start)
     hi, lo = np.asarray(tid[:, 0], np.uint64), np.asarray(tid[:, 1], np.uint64)
     start = np.asarray(start, np.uint64)
@@ -112,11 +135,15 @@ def pack(tid: np.ndarray, start, end, status, svc, svc_str, ep, world: int, attr
     status = np.asarray(status, np.uint8)
     svc = np.asarray(svc, np.int64)
     slot = lay.slot_of(svc)
-    svcb = lay.svc_rule_bits(svc_str)
-    if attr is not None:
-        svcb |= np.asarray(attr, np.uint64) << np.uint64(lay.attr_shift)
-    srm = np.array([lay.slot_rules.get(k, 0) for k in range(len(lay.slot))] + [0], dtype=np.uint64)
-    ep = np.asarray(ep, np.uint64) & srm[slot]   # slot -1 -> the trailing 0
+    ep = np.asarray(ep, np.uint64).reshape(len(chunks), n)
+    eps, svcbs = [], []
+    for k, ck in enumerate(chunks):
+        sb = ck.svc_rule_bits(svc_str)
+        if attr is not None:
+            sb |= np.asarray(attr, np.uint64) << np.uint64(ck.attr_shift)
+        srm = np.array([ck.slot_rules.get(j, 0) for j in range(len(ck.slot))] + [0], dtype=np.uint64)
+        eps.append(ep[k] & srm[ck.slot_of(svc)])   # slot -1 -> the trailing 0
+        svcbs.append(sb)
     idx = np.arange(n)
     head = np.ones(n, dtype=bool)
     if n > 1:
@@ -124,7 +151,7 @@ def pack(tid: np.ndarray, start, end, status, svc, svc_str, ep, world: int, attr
     head |= (idx % STEP) == 0
     starts = np.flatnonzero(head)
     ends = np.append(starts[1:], n)
-    recs = np.zeros(len(starts), dtype=XDT)
+    recs = np.zeros(len(starts), dtype=xdt(len(chunks)))
     for k, (a, b) in enumerate(zip(starts, ends)):
         f, m, e = 0, INF, np.uint64(0)
         if slot[a] >= 0:
@@ -138,8 +165,8 @@ def pack(tid: np.ndarray, start, end, status, svc, svc_str, ep, world: int, attr
                 e = max(e, end[i])
         flags = (XERR if np.any(status[a:b] == native.STATUS_ERROR) else 0) | (XLAT if f & 2 else 0) | \
             (XRESET if f & 1 else 0)
-        recs[k] = (hi[a], lo[a], m, e, (int(svc[a]) if slot[a] >= 0 else NONE24) | (flags << 24),
-                   np.bitwise_or.reduce(ep[a:b]), np.bitwise_or.reduce(svcb[a:b]))
+        recs[k] = (hi[a], lo[a], m, e, (int(svc[a]) if slot[a] >= 0 else NONE24) | (flags << 24)) + tuple(
+            np.bitwise_or.reduce(w[a:b]) for c in range(len(chunks)) for w in (eps[c], svcbs[c]))
     own = owners(recs["hi"], recs["lo"], world)
     order = np.argsort(own, kind="stable")
     slot_of_rec = np.empty(len(starts), dtype=np.int64)
@@ -173,9 +200,11 @@ class HostCols:
             setattr(self.cols, k, v.ctypes.data)
 
 
-def unpack(recv: np.ndarray) -> HostCols:
-    """The owner-side columns ose_shard_unpack writes (one span per record)."""
-    r = recv.view(XDT)
+def unpack(recv: np.ndarray, chunks: int = 1) -> HostCols:
+    """The owner-side columns ose_shard_unpack writes (one span per record;
+    route_match / svc_match: plane k for rule chunk k)."""
+    r = recv.view(xdt(chunks))
+    ep, sb = chunk_words(r, chunks)
     flags = (r["w4"] >> np.uint64(24)).astype(np.int64) & 0xFF
     sv = (r["w4"] & np.uint64(NONE24)).astype(np.int64)
     lat = (flags & XLAT) != 0
@@ -185,8 +214,8 @@ def unpack(recv: np.ndarray) -> HostCols:
               np.where(lat & ((flags & XRESET) != 0) & (r["m"] != INF), 0x80, 0)).astype(np.uint8)
     svc = np.where(lat & (sv != NONE24), sv, 0xFFFFFFFF).astype(np.uint32)
     tid = np.stack([r["hi"], r["lo"]], axis=1)
-    return HostCols(tid, start, end, status, svc, np.full(len(r), 0xFFFFFFFF, np.uint32), r["ep"],
-                    svc_match=r["svcb"])
+    return HostCols(tid, start, end, status, svc, np.full(len(r), 0xFFFFFFFF, np.uint32), ep.reshape(-1),
+                    svc_match=sb.reshape(-1))
 
 
 def expand_for_oracle(recv: np.ndarray, cfg: dict):

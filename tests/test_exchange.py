@@ -382,7 +382,7 @@ def test_gpu_owner_decide_vs_general(case):
 
 @pytest.mark.gpu
 def test_gpu_owner_decide_overflow_falls_back():
-    # a trace received as 600 pieces overflows its bucket (512 records): the
+    # a trace received as 600 pieces overflows its bucket (kOwnerCap, 256 records): the
     # whole batch takes the general path, with the same decisions
     import torch
     from odigos_amd.batch import Generator
