@@ -75,7 +75,8 @@ extern "C" {
  *                   processor.go:214-233)
  *   PATH_*          which source calculateTemplatedUrlFromAttr uses
  *                   (processor.go:113-147, 188-212): RAW = url.path, or the
- *                   Path of url.full/http.url after net/url.Parse on the host;
+ *                   Path of url.full/http.url after net/url.Parse (on the host,
+ *                   or on the GPU under the engine option "otlp_url_full");
  *                   TARGET = http.target, the engine cuts at the first '?';
  *                   NONE = no source, or url.Parse failed.                     */
 #define OSE_URL_HAS_METHOD      0x01u
@@ -435,8 +436,22 @@ int ose_engine_attr_key(const ose_engine* eng, uint32_t k, const char** key, uin
  *   "otlp_host_resources"  ResourceSpans on the host, ScopeSpans on the GPU
  *   "otlp_host_scopes"     ResourceSpans and ScopeSpans on the host
  *   "encode_host"          ose_otlp_encode always uses the host encoder
- * and two feature switches:
- *   "otlp_sqlop"           the OTLP path carries odigossqldboperationprocessor:
+ * and three feature switches:
+ *   "otlp_url_full"        ose_otlp_decode computes the Path of
+ *                          net/url.Parse(url.full | http.url) on the GPU for
+ *                          every span whose chosen value is a string_value
+ *                          (a pass behind the span kernel; a Path that holds
+ *                          escapes is unescaped into the arena after the host
+ *                          pass's strings): such spans no longer take the host
+ *                          pass.  The columns are the same with it on and off;
+ *                          ose_otlp_url_full_counts is the witness.  A value
+ *                          that is not a string still takes the host pass.
+ *                          OSE_EINVAL on an engine without the
+ *                          odigosurltemplate section.  Off by default (every
+ *                          entry point then answers as before, and a decode
+ *                          allocates, launches, copies and waits for nothing
+ *                          more); on by default from the next ABI version.
+ *   "otlp_sqlop"          the OTLP path carries odigossqldboperationprocessor:
  *                          ose_otlp_decode fills db_flags / db_query /
  *                          res_sql_ok, ose_otlp_encode applies sql_op, and
  *                          ose_otlp_pipeline_create accepts OSE_STAGE_SQLOP.
@@ -644,7 +659,10 @@ int ose_allreduce_counters(const int64_t* local, int64_t* node, uint64_t n, void
  * "otlp_sqlop" a second GPU pass reads db.query.text / db.operation.name of
  * every span (db_flags, db_query; a query value that is not a string takes
  * the host pass for AsString) and res_sql_ok comes with the resource columns
- * (telemetry.sdk.language).  What UnmarshalTraces rejects is
+ * (telemetry.sdk.language).  Under "otlp_url_full" a GPU pass parses the
+ * url.full / http.url strings, which then need no host pass; the paths that
+ * hold escapes are unescaped into the arena behind the host pass's strings.
+ * What UnmarshalTraces rejects is
  * OSE_EINVAL.  Asynchronous work is on hip_stream; the call returns when
  * the columns are complete on that stream.  res_attrset ids index the
  * attribute sets ose_otlp_attrset returns ({"key": "value", ...}).         */
@@ -657,6 +675,11 @@ void ose_host_free(void* p);
 int ose_otlp_decode(ose_engine* eng, const void* pb, size_t len, void* hip_stream, ose_otlp_batch** out);
 const ose_columns* ose_otlp_columns(const ose_otlp_batch* b);   /* device pointers */
 uint32_t ose_otlp_host_spans(const ose_otlp_batch* b);
+/* engine option "otlp_url_full": out[0] the spans whose url.full / http.url
+ * string the GPU parsed at the decode, out[1] the unescaped path bytes it wrote
+ * into the arena; both 0 with the option off.  OSE_ENOTSUP for a batch
+ * released by a groupbytrace store.                                         */
+int ose_otlp_url_full_counts(const ose_otlp_batch* b, uint64_t out[2]);
 /* which path the decode took (read-only): out[0] the TracesData chain was
  * linked on the GPU (engine option otlp_gpu_chain), [1] resources the device
  * table missed, [2] of them keyed into the table (one Resource field or

@@ -76,6 +76,9 @@ class Generator:
             L.osegen_otlp_scoped.restype = C.c_void_p
             L.osegen_otlp_scoped.argtypes = [C.POINTER(native.Columns), C.c_int, C.POINTER(C.c_uint64), C.c_uint32,
                                              C.c_char_p, C.c_void_p, C.c_uint32]
+            L.osegen_otlp_url_full.restype = C.c_void_p
+            L.osegen_otlp_url_full.argtypes = [C.POINTER(native.Columns), C.c_int, C.POINTER(C.c_uint64), C.c_uint32,
+                                               C.c_uint32]
             L.osegen_otlp_free.argtypes = [C.c_void_p]
             Generator._L = L
         if world is None:
@@ -95,12 +98,19 @@ class Generator:
             n = (n + 15) // 16 * 16 + 16
         return host_array(getattr(self.cols, field), n)
 
-    def otlp(self, threads: int = 8, sql_every: int = 0, scope_names=None) -> bytes:
+    def otlp(self, threads: int = 8, sql_every: int = 0, scope_names=None, url_full: float = 0.0) -> bytes:
         """The batch as a serialized OTLP TracesData (gen_otlp.cpp); sql_every:
         one span in that many also carries a db.query.text (0: none);
-        scope_names: every resource's scope name is drawn from this list."""
+        scope_names: every resource's scope name is drawn from this list;
+        url_full: that share of the spans with a method and a path source
+        carries url.full alone (scheme, host, the same path, a query; a tenth
+        of them with an escaped segment more)."""
         n = C.c_uint64()
-        if scope_names:
+        if url_full:
+            assert not scope_names
+            p = Generator._L.osegen_otlp_url_full(C.byref(self.cols), threads, C.byref(n), sql_every,
+                                                  int(round(url_full * 1_000_000)))
+        elif scope_names:
             bs = [s.encode() for s in scope_names]
             lens = np.array([len(b) for b in bs], dtype=np.uint32)
             p = Generator._L.osegen_otlp_scoped(C.byref(self.cols), threads, C.byref(n), sql_every, b"".join(bs),
@@ -292,7 +302,8 @@ class Engine:
     def set_option(self, name: str, value: int = 1):
         """ose_engine_set_option: the alternative OTLP legs (tests), and
         "url_regex_nfa": every odigosurltemplate regexp as an NFA program
-        (set between calls).  Once
+        (set between calls), and "otlp_url_full": ose_otlp_decode parses
+        url.full / http.url on the GPU (OtlpBatch.url_full_counts).  Once
         "url_path_counts" has been turned on, path_counts() keeps its two URL
         keys for this engine, also after the option is turned off again."""
         native.check(self.L.ose_engine_set_option(self.h, name.encode(), int(value)))
@@ -635,6 +646,11 @@ class OtlpBatch:
         engine.adopt(self)
         self.cols = native.Columns.from_buffer_copy(self.L.ose_otlp_columns(h).contents)
         self.host_spans = int(self.L.ose_otlp_host_spans(h))
+        # engine option otlp_url_full: (spans whose url.full / http.url the GPU
+        # parsed, unescaped path bytes it wrote); zeros with the option off
+        uc = (C.c_uint64 * 2)()
+        native.check(self.L.ose_otlp_url_full_counts(h, uc))
+        self.url_full_counts = (int(uc[0]), int(uc[1]))
         wi = (C.c_uint32 * 8)()
         native.check(self.L.ose_otlp_walk_info(h, wi))
         self.walk_info = dict(zip(WALK_INFO, list(wi)))

@@ -765,6 +765,7 @@ int ose_engine_set_option(ose_engine* eng, const char* name, int64_t value) {
       {"url_path_counts", Engine::kOptUrlPathCounts},
       {"otlp_condattr", Engine::kOptOtlpCondattr},
       {"url_regex_nfa", Engine::kOptUrlRegexNfa},
+      {"otlp_url_full", Engine::kOptOtlpUrlFull},
   };
   // the two options that carry a number (engine_internal.hpp url_tail_slices_opt)
   if (strcmp(name, "url_tail_slices") == 0) {
@@ -781,6 +782,8 @@ int ose_engine_set_option(ose_engine* eng, const char* name, int64_t value) {
     if (strcmp(name, o.name) != 0) continue;
     if (o.bit == Engine::kOptOtlpSqlop && !e->has_sqlop)
       return fail(OSE_EINVAL, "engine option otlp_sqlop: odigossqldboperationprocessor is not configured");
+    if (o.bit == Engine::kOptOtlpUrlFull && !e->has_url)
+      return fail(OSE_EINVAL, "engine option otlp_url_full: odigosurltemplate is not configured");
     if (o.bit == Engine::kOptOtlpCondattr) {
       if (!e->has_condattr)
         return fail(OSE_EINVAL, "engine option otlp_condattr: odigosconditionalattributes is not configured");

@@ -197,7 +197,10 @@ struct Engine {
     // a test and measurement seam: the URL tables rebuilt with every user
     // regexp as an NFA program (url_blob_forced_dev), so a config whose
     // regexps have DFAs runs both routes; set between calls, not during one
-    kOptUrlRegexNfa = 128
+    kOptUrlRegexNfa = 128,
+    // a feature switch like kOptOtlpSqlop: ose_otlp_decode parses url.full / http.url
+    // on the GPU (otlp_url_full_kernel.hip; off until the next ABI version)
+    kOptOtlpUrlFull = 256
   };
   std::atomic<uint32_t> options{0};
   bool option(uint32_t o) const { return (options.load(std::memory_order_relaxed) & o) != 0; }

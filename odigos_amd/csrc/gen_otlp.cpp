@@ -83,8 +83,12 @@ struct ScopeNames {
 };
 
 // sql_every != 0: one span in sql_every also carries a db.query.text (its last attribute)
+// url_full_ppm: that share (in millionths) of the spans with a method and a
+// path source carries url.full alone in its place, as a client instrumentation
+// under the stable HTTP conventions sends it: scheme, host and port, the same
+// path, a query; a tenth of them with one more, escaped, segment
 void encode_resources(const ose_columns* c, const std::vector<Res>& res, size_t r0, size_t r1, std::string& out,
-                      uint32_t sql_every, const ScopeNames& names) {
+                      uint32_t sql_every, const ScopeNames& names, uint32_t url_full_ppm) {
   std::string rs, sc, sp, tmp;
   for (size_t r = r0; r < r1; r++) {
     rs.clear();
@@ -149,9 +153,20 @@ void encode_resources(const ose_columns* c, const std::vector<Res>& res, size_t 
         kv_str(sp, 9, "http.route", (const char*)c->arena + rt.off, rt.len);
       if (c->kind[i] == OSE_KIND_CLIENT && tgt == OSE_URL_TGT_STR) kv_str(sp, 9, "url.template", "/t/{id}", 7);
       const ose_strref p = c->path[i];
-      if ((f & OSE_URL_PATH_MASK) == OSE_URL_PATH_RAW) kv_str(sp, 9, "url.path", (const char*)c->arena + p.off, p.len);
-      if ((f & OSE_URL_PATH_MASK) == OSE_URL_PATH_TARGET)
+      if (url_full_ppm && (f & OSE_URL_HAS_METHOD) && (f & OSE_URL_PATH_MASK) != OSE_URL_PATH_NONE &&
+          mix(h ^ 0xF0115) % 1000000 < url_full_ppm) {
+        const char* path = (const char*)c->arena + p.off;
+        const void* q = std::memchr(path, '?', p.len);
+        tmp.assign("https://api.internal.svc:8443");
+        tmp.append(path, q ? (size_t)((const char*)q - path) : p.len);
+        if (mix(h ^ 0xE5CA9) % 10 == 0) tmp.append("/caf%C3%A9%20menu");
+        tmp.append("?page=2&sort=asc");
+        kv_str(sp, 9, "url.full", tmp.data(), tmp.size());
+      } else if ((f & OSE_URL_PATH_MASK) == OSE_URL_PATH_RAW) {
+        kv_str(sp, 9, "url.path", (const char*)c->arena + p.off, p.len);
+      } else if ((f & OSE_URL_PATH_MASK) == OSE_URL_PATH_TARGET) {
         kv_str(sp, 9, "http.target", (const char*)c->arena + p.off, p.len);
+      }
       if (f & OSE_URL_HAS_METHOD) {   // what an HTTP instrumentation adds next to them
         kv_int(sp, 9, "http.response.status_code", c->status[i] == OSE_STATUS_ERROR ? 500 : 200);
         static const char kUa[] = "Mozilla/5.0 (X11; Linux x86_64) odigos-bench/1.0";
@@ -188,8 +203,11 @@ extern "C" {
 // on one span in sql_every (0: none), for the odigossqldboperationprocessor legs.
 // osegen_otlp_scoped: the same with every resource's scope name drawn from
 // n_names names (their bytes back to back in `names`, lengths in name_lens),
-// for the odigosconditionalattributes legs.
-static char* otlp_bytes(const ose_columns* c, int threads, uint64_t* len, uint32_t sql_every, const ScopeNames& names) {
+// for the odigosconditionalattributes legs.  osegen_otlp_url_full: the same as
+// osegen_otlp_sql with url.full alone on url_full_ppm millionths of the spans
+// that have a method and a path source (encode_resources).
+static char* otlp_bytes(const ose_columns* c, int threads, uint64_t* len, uint32_t sql_every, const ScopeNames& names,
+                        uint32_t url_full_ppm = 0) {
   std::vector<Res> res(c->n_resources, Res{0, 0});
   for (uint64_t i = 0; i < c->n_spans; i++) {
     const uint32_t r = c->resource[i];
@@ -201,7 +219,7 @@ static char* otlp_bytes(const ose_columns* c, int threads, uint64_t* len, uint32
   std::vector<std::string> parts((size_t)threads);
   std::vector<std::thread> th;
   for (int t = 0; t < threads; t++)
-    th.emplace_back([&, t]() { encode_resources(c, res, R * t / threads, R * (t + 1) / threads, parts[t], sql_every, names); });
+    th.emplace_back([&, t]() { encode_resources(c, res, R * t / threads, R * (t + 1) / threads, parts[t], sql_every, names, url_full_ppm); });
   for (auto& x : th) x.join();
   uint64_t total = 0;
   for (auto& p : parts) total += p.size();
@@ -230,6 +248,10 @@ char* osegen_otlp_scoped(const ose_columns* c, int threads, uint64_t* len, uint3
     off += name_lens[k];
   }
   return otlp_bytes(c, threads, len, sql_every, sn);
+}
+
+char* osegen_otlp_url_full(const ose_columns* c, int threads, uint64_t* len, uint32_t sql_every, uint32_t url_full_ppm) {
+  return otlp_bytes(c, threads, len, sql_every, ScopeNames{}, url_full_ppm);
 }
 
 char* osegen_otlp(const ose_columns* c, int threads, uint64_t* len) { return osegen_otlp_sql(c, threads, len, 0); }

@@ -628,7 +628,7 @@ enum : uint32_t {
   kRoleUrlTmpl = 1u << 3,     // url.template (CLIENT target)
   kRoleUrlPath = 1u << 4,     // url.path
   kRoleTarget = 1u << 5,      // http.target
-  kRoleFull = 1u << 6,        // url.full / http.url: net/url.Parse on the host
+  kRoleFull = 1u << 6,        // url.full / http.url: net/url.Parse on the host (otlp_url_full: otlp_url_full_kernel.hip)
   kRoleHost = 1u << 7,        // a json span_attribute rule's key: host pass
 };
 constexpr uint64_t kRoleAttr0 = 1ull << 8;   // << k: GPU attribute key column k (k < kOtlpMaxAttrKeys)
@@ -664,6 +664,7 @@ struct OtlpArgs {
   uint32_t* host_count;         // zeroed before launch
   uint32_t* host_list;
   uint32_t host_cap;
+  uint32_t url_full;            // engine option otlp_url_full: a url.full / http.url source alone lists no span
 };
 // ScopeSpans walked on the GPU (the host walks TracesData and ResourceSpans
 // only): pass 1 counts each scope's spans and reads its InstrumentationScope
@@ -941,6 +942,35 @@ struct OtlpSqlFix {
   ose_strref query;
 };
 void launch_otlp_sqlop_fix(const OtlpSqlFix* fix, uint32_t n, uint8_t* db_flags, ose_strref* db_query, hipStream_t st);
+
+// The Path of net/url.Parse(url.full | http.url) from the message
+// (otlp_url_full_kernel.hip, url_full.hpp; engine option otlp_url_full).  A
+// pass of its own after the span kernel, one lane per span it finished with
+// OSE_URL_HAS_METHOD and OSE_URL_PATH_NONE: the first url.full KeyValue, else
+// the first http.url.  A value that is not a string_value needs AsString: the
+// span joins the host pass's list.  A Path without escapes is a ref into the
+// message bytes (OSE_URL_PATH_RAW); one with escapes parks its raw sub-range
+// in path[i] and its decoded length in dec_len[i].  After a scan of dec_len
+// (dec_off) and room in the arena, launch_otlp_url_full_unescape writes the
+// decoded bytes at arena + dec_base + dec_off[i] and points path[i] there.
+struct OtlpUrlFullArgs {
+  const uint8_t* pb;            // as OtlpArgs::pb
+  uint64_t n_spans;
+  const uint64_t* span_ref;
+  uint8_t* url_flags;
+  ose_strref* path;
+  uint32_t* dec_len;            // [n_spans] written for every span (0: nothing to unescape)
+  const uint32_t* dec_off;      // the unescape pass: exclusive scan of dec_len
+  uint32_t* parsed;             // += the spans whose string value was parsed here (zeroed before launch)
+  uint8_t* out;                 // the unescape pass: the arena (pb may be the same buffer; the regions are disjoint)
+  uint32_t dec_base;
+  uint8_t* host_flag;           // the span kernel's; 1: skipped here
+  uint32_t* host_count;
+  uint32_t* host_list;
+  uint32_t host_cap;
+};
+void launch_otlp_url_full(const OtlpUrlFullArgs& a, hipStream_t st);
+void launch_otlp_url_full_unescape(const OtlpUrlFullArgs& a, hipStream_t st);
 
 // odigosconditionalattributes' span columns from the message
 // (otlp_condattr_kernel.hip; engine option otlp_condattr).  A pass of its own

@@ -31,6 +31,9 @@ struct OtlpBatchImpl {
   DevBuf arena, slab, stage, fixdev;   // device arena; device columns; pinned staging; host-pass records
   std::vector<std::vector<std::pair<std::string, std::string>>> attrsets;
   uint32_t host_spans = 0;
+  // engine option otlp_url_full (ose_otlp_url_full_counts): the spans whose
+  // url.full / http.url the GPU parsed, the decoded path bytes it wrote
+  uint64_t url_full_counts[2] = {0, 0};
   // which path the decode took (ose_otlp_walk_info): [0] the GPU chain linked,
   // [1] resource-table misses, [2] of them entered into the table's key space
   // (one Resource field or none), [3] scopes the host sized, [4] the scope

@@ -19,12 +19,16 @@
 //      db.operation.name (db_flags, db_query) and may add spans to the list;
 //      under otlp_condattr, otlp_condattr_kernel reads the first KeyValue of
 //      each odigosconditionalattributes key (ose_otlp_condattr_columns) and may
-//      add spans too;
+//      add spans too; under otlp_url_full, otlp_url_full_kernel last parses the
+//      url.full / http.url of the spans whose path has no other source
+//      (url_full.hpp), and a scan places the paths that hold escapes;
 //   4. host_pass: the spans they list get pb_span + columnize_span, their
 //      strings appended after the message bytes (regrow_arena), written by
 //      otlp_fix_kernel (and otlp_sqlop_fix_kernel); under otlp_condattr that
 //      stage's entries of the listed spans and its per-scope and per-resource
-//      columns are then made on the host (condattr_finish).
+//      columns are then made on the host (condattr_finish).  Between the two,
+//      url_full_unescape writes the unescaped url.full paths behind the host
+//      pass's strings.
 #include <algorithm>
 #include <chrono>
 #include <deque>
@@ -42,6 +46,7 @@
 #include "otlp_encode.hpp"
 #include "otlp_pb.hpp"
 #include "taskpool.hpp"
+#include "url_full.hpp"
 
 namespace ose {
 
@@ -1144,6 +1149,12 @@ int regrow_arena(OtlpBatchImpl* b, size_t keep, size_t want, hipStream_t st) {
 
 namespace {
 // ---- ose_otlp_decode's steps (decode() below calls them in this order) ----------
+// Engine option otlp_url_full: the per-span decoded lengths, their exclusive
+// scan and the scan's tile status (column_slab carves them), and the words
+// that follow the host list's count under the option, fetched with it
+struct UrlFullCols { uint32_t *dec_len = nullptr, *dec_off = nullptr; uint64_t* status = nullptr; uint32_t tiles = 0; };
+enum : int { kUfTotal = 1, kUfParsed = 2, kUfScanError = 3, kUfCounter = 4 };   // [0]: the list's count
+constexpr size_t kUfWordBytes = 32;
 // the span columns as the span kernel and the host pass's fix kernel write them
 template <class Args>
 void set_span_columns(Args& a, const ose_columns& c) {
@@ -1230,7 +1241,8 @@ int walk_scopes(Engine* e, OtlpEngine* o, OtlpBatchImpl* b, const uint8_t* pb, s
 //     not leave on the device go up through staging, the span kernels' outputs
 //     follow.  *span_ref_out: the spans' refs, *hl: the host-pass list (count zeroed).
 int column_slab(OtlpEngine* o, OtlpBatchImpl* b, Walked& w, const OtlpResArgs& ra, bool gpu_scopes, bool gpu_res,
-                bool sql, uint64_t n, uint64_t R, uint64_t S, hipStream_t st, uint64_t** span_ref_out, HostList* hl) {
+                bool sql, uint64_t n, uint64_t R, uint64_t S, hipStream_t st, uint64_t** span_ref_out, HostList* hl,
+                UrlFullCols* uf) {
   ose_columns& c = b->cols;   // (scope_size / scope_resource are set by the GPU scope walk)
   const uint32_t K = o->n_attr_keys;
   b->attrsets = std::move(w.sets);
@@ -1260,8 +1272,14 @@ int column_slab(OtlpEngine* o, OtlpBatchImpl* b, Walked& w, const OtlpResArgs& r
       {(void**)&c.status, N}, {(void**)&c.kind, N}, {(void**)&c.url_flags, N},
       {(void**)&c.path, 8 * N}, {(void**)&c.route, 8 * N}, {(void**)&c.span_size, 4 * N},
       {(void**)&c.name_len, 4 * N},
-      {(void**)&hl->flag, N}, {(void**)&hl->count, 16}, {(void**)&hl->list, 4 * N},
+      {(void**)&hl->flag, N}, {(void**)&hl->count, uf ? kUfWordBytes : 16}, {(void**)&hl->list, 4 * N},
   });
+  if (uf) {   // engine option otlp_url_full: the decoded lengths, their scan and its tile status
+    uf->tiles = (uint32_t)((N + kScanTileItems - 1) / kScanTileItems);
+    parts.push_back({(void**)&uf->dec_len, 4 * N});
+    parts.push_back({(void**)&uf->dec_off, 4 * N});
+    parts.push_back({(void**)&uf->status, 8 * (size_t)uf->tiles});
+  }
   if (o->json_rules) parts.push_back({(void**)&c.attr_match, 8 * N * (size_t)o->attr_words});
   if (sql) {
     parts.push_back({(void**)&c.db_flags, N});
@@ -1274,7 +1292,8 @@ int column_slab(OtlpEngine* o, OtlpBatchImpl* b, Walked& w, const OtlpResArgs& r
   SlabSize z;
   if (int rc = slab_place(b->slab, parts, &b->stage, &z)) return rc;
   if (z.inputs) HIP_TRY(hipMemcpyAsync(b->slab.p, b->stage.p, z.inputs, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemsetAsync(hl->count, 0, 16, st));
+  HIP_TRY(hipMemsetAsync(hl->count, 0, uf ? kUfWordBytes : 16, st));
+  if (uf) HIP_TRY(hipMemsetAsync(uf->status, 0, 8 * (size_t)uf->tiles, st));
   if (gpu_res) {   // the resource columns the GPU pass wrote
     c.res_svc = ra.res_svc;
     c.res_svc_str = ra.res_svc_str;
@@ -1310,7 +1329,7 @@ int column_slab(OtlpEngine* o, OtlpBatchImpl* b, Walked& w, const OtlpResArgs& r
 // 3. the GPU decoder: otlp_span_kernel, then (sql) otlp_sqlop_kernel and (ca)
 //    otlp_condattr_kernel; *cnt: the spans on the host-pass list once they have run
 int span_kernels(Engine* e, OtlpEngine* o, OtlpBatchImpl* b, uint64_t n, const uint64_t* span_ref, const HostList& hl,
-                 bool sql, bool ca, hipStream_t st, uint32_t* cnt) {
+                 bool sql, bool ca, const UrlFullCols* uf, hipStream_t st, uint32_t* cnt) {
   const ose_columns& c = b->cols;
   OtlpArgs a{};
   a.pb = b->arena.p;
@@ -1324,6 +1343,7 @@ int span_kernels(Engine* e, OtlpEngine* o, OtlpBatchImpl* b, uint64_t n, const u
   a.key_lens = o->key_lens;
   set_span_columns(a, c);
   set_host_list(a, hl);
+  a.url_full = uf ? 1u : 0u;
   (void)hipGetLastError();   // a stale error of an earlier call must not be reported as this launch's
   if (const int rc = e->timed("otlp_span_kernel", st, [&] {
         if (n) b->walk_info[6] = launch_otlp_spans(a, st);
@@ -1341,10 +1361,56 @@ int span_kernels(Engine* e, OtlpEngine* o, OtlpBatchImpl* b, uint64_t n, const u
   }
   if (ca)
     if (int rc = condattr_spans(e, b, n, span_ref, hl, st)) return rc;
-  *cnt = 0;
-  HIP_TRY(hipMemcpyAsync(cnt, hl.count, 4, hipMemcpyDeviceToHost, st));
+  if (uf && n) {
+    // the Path of url.full / http.url: a pass of its own, last, so the list it
+    // skips is final; then the decoded paths' places in span order (the same
+    // arena on every run)
+    OtlpUrlFullArgs ua{};
+    ua.pb = b->arena.p;
+    ua.n_spans = n;
+    ua.span_ref = span_ref;
+    ua.url_flags = const_cast<uint8_t*>(c.url_flags);
+    ua.path = const_cast<ose_strref*>(c.path);
+    ua.dec_len = uf->dec_len;
+    ua.parsed = hl.count + kUfParsed;
+    set_host_list(ua, hl);
+    if (const int rc = e->timed("otlp_url_full_kernel", st, [&] { launch_otlp_url_full(ua, st); })) return rc;
+    if (const int rc = scan_counts(n, uf->tiles, uf->dec_len, uf->dec_off, uf->status, hl.count, kUfTotal, kUfCounter,
+                                   kUfScanError, st))
+      return rc;
+  }
+  uint32_t h[4] = {0, 0, 0, 0};   // the list's count; under otlp_url_full the words beside it ride along
+  HIP_TRY(hipMemcpyAsync(h, hl.count, uf ? 16 : 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
+  if (h[kUfScanError]) return fail(OSE_EDEVICE, "OTLP ingest: url.full scan error");
+  *cnt = h[0];
   b->host_spans = *cnt;
+  b->url_full_counts[0] = h[kUfParsed];
+  b->url_full_counts[1] = h[kUfTotal];
+  return 0;
+}
+
+// 4b. engine option otlp_url_full: the url.full paths that hold escapes,
+//     unescaped behind what the arena holds (the message bytes, then the host
+//     pass's strings; 16 bytes of slack between and after)
+int url_full_unescape(OtlpBatchImpl* b, const UrlFullCols& uf, hipStream_t st) {
+  ose_columns& c = b->cols;
+  const uint64_t total = b->url_full_counts[1];
+  const size_t base = up(c.arena_bytes + 16, 16), end = base + total;
+  if (end > 0xFFFFFFF0ull) return fail(OSE_ERANGE, "OTLP ingest: the arena passes 4 GiB");
+  if (int rc = regrow_arena(b, base, end + 16, st)) return rc;   // what the arena holds moves with it, slack included
+  OtlpUrlFullArgs ua{};
+  ua.pb = b->arena.p;
+  ua.out = b->arena.p;
+  ua.n_spans = c.n_spans;
+  ua.url_flags = const_cast<uint8_t*>(c.url_flags);
+  ua.path = const_cast<ose_strref*>(c.path);
+  ua.dec_len = uf.dec_len;
+  ua.dec_off = uf.dec_off;
+  ua.dec_base = (uint32_t)base;
+  if (const int rc = b->e->timed("otlp_url_full_unescape_kernel", st, [&] { launch_otlp_url_full_unescape(ua, st); }))
+    return rc;
+  c.arena_bytes = end;
   return 0;
 }
 
@@ -1498,6 +1564,9 @@ int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchIm
   // engine option otlp_condattr: odigosconditionalattributes' columns are decoded too
   const bool ca = e->has_condattr && e->option(Engine::kOptOtlpCondattr);
   b->ca_on = false;
+  // engine option otlp_url_full: the Path of url.full / http.url is parsed on the GPU
+  const bool url_full = e->has_url && e->option(Engine::kOptOtlpUrlFull);
+  b->url_full_counts[0] = b->url_full_counts[1] = 0;
   // the walk: TracesData and ResourceSpans on the host, ScopeSpans up to
   // 64 KB on the GPU (engine option otlp_host_scopes: all on the host)
   // (otlp_host_resources: ResourceSpans on the host, ScopeSpans on the
@@ -1523,13 +1592,16 @@ int decode(Engine* e, const uint8_t* pb, size_t len, hipStream_t st, OtlpBatchIm
   }
   uint64_t* span_ref = nullptr;
   HostList hl;
-  if ((rc = column_slab(o, b, w, ra, gpu_scopes, gpu_res, sql, n, R, S, st, &span_ref, &hl))) return rc;
+  UrlFullCols uf;
+  if ((rc = column_slab(o, b, w, ra, gpu_scopes, gpu_res, sql, n, R, S, st, &span_ref, &hl, url_full ? &uf : nullptr)))
+    return rc;
   lap(2);
   uint32_t cnt = 0;
-  if ((rc = span_kernels(e, o, b, n, span_ref, hl, sql, ca, st, &cnt))) return rc;
+  if ((rc = span_kernels(e, o, b, n, span_ref, hl, sql, ca, url_full ? &uf : nullptr, st, &cnt))) return rc;
   lap(3);
   std::vector<uint32_t> list;   // the host pass's spans: none without a count
   if (cnt && (rc = host_pass(o, b, pb, w, gpu_res, sql, cnt, hl.list, st, list))) return rc;
+  if (b->url_full_counts[1] && (rc = url_full_unescape(b, uf, st))) return rc;
   if (ca && (rc = condattr_finish(e, b, pb, list, hl.list, st))) return rc;
   if (cnt) lap(4);
   return 0;
@@ -1621,6 +1693,24 @@ int ose_otlp_decode(ose_engine* eng, const void* pb, size_t len, void* hip_strea
   return 0;
 }
 
+// Test seam (CPU): url_full.hpp's host instantiation on one string.  out[4]:
+// the outcome (0 error, 1 empty, 2 in place, 3 decoded), the Path's sub-range
+// (offset, length) and its decoded length; `decoded` (may be NULL, else at
+// least len bytes) takes the Path's bytes: the sub-range as it is, or unescaped.
+int osehost_url_full_parse(const char* s, size_t len, uint32_t out[4], uint8_t* decoded) {
+  if ((!s && len) || !out) return fail(OSE_EINVAL, "NULL argument");
+  if (len > 0xFFFFFFF0ull) return fail(OSE_ERANGE, "osehost_url_full_parse: string beyond 4 GiB");
+  urlfull::ViewSrc src{s};
+  const urlfull::Result r = urlfull::parse(src, 0, (uint32_t)len);
+  out[0] = r.outcome;
+  out[1] = r.off;
+  out[2] = r.len;
+  out[3] = r.dec_len;
+  if (decoded && r.outcome == urlfull::kDecoded) urlfull::unescape_into(src, r.off, r.len, decoded);
+  else if (decoded && r.outcome == urlfull::kInPlace) std::memcpy(decoded, s + r.off, r.len);
+  return 0;
+}
+
 // Test seam (CPU): the structural walk alone, for a pipeline config
 // {"odigossampling": ..., "odigosurltemplate": ..., "odigostrafficmetrics": ...};
 // the arrays as JSON, NULL on an error (osehost_last_error)
@@ -1700,6 +1790,16 @@ int ose_otlp_timings(const ose_otlp_batch* bb, double* ms5) {
   if (reinterpret_cast<const OtlpBatchImpl*>(bb)->released)
     return fail(OSE_ENOTSUP, "ose_otlp_timings: a batch released by a groupbytrace store was not decoded");
   std::memcpy(ms5, reinterpret_cast<const OtlpBatchImpl*>(bb)->t_ms, sizeof(double) * 5);
+  return 0;
+}
+
+int ose_otlp_url_full_counts(const ose_otlp_batch* bb, uint64_t out[2]) {
+  if (!bb || !out) return fail(OSE_EINVAL, "NULL argument");
+  const auto* b = reinterpret_cast<const OtlpBatchImpl*>(bb);
+  if (b->released)
+    return fail(OSE_ENOTSUP, "ose_otlp_url_full_counts: a batch released by a groupbytrace store was not decoded");
+  out[0] = b->url_full_counts[0];
+  out[1] = b->url_full_counts[1];
   return 0;
 }
 

@@ -13,7 +13,9 @@
 // the arena.  A span the lane cannot finish exactly — a value that needs
 // AsString or url.Parse, a nested ArrayValue / KeyValueList, a json
 // span_attribute key, an id of unusual length, a group or malformed field,
-// a repeated KeyValue field — is listed for the host pass (otlp_host.cpp),
+// a repeated KeyValue field — is listed for the host pass (otlp_host.cpp; under the
+// engine option otlp_url_full a url.full / http.url source alone is not: the pass in
+// otlp_url_full_kernel.hip parses it),
 // which decodes it with the host unmarshaler and writes all its columns.
 #include <hip/hip_runtime.h>
 
@@ -292,8 +294,8 @@ __device__ __forceinline__ void decode_span(const OtlpArgs& a, const KeyTab& kt,
         uf |= OSE_URL_PATH_TARGET;
         if (target.type != OSE_ATTR_STR) host = true;
         path = ose_strref{target.off, target.len};
-      } else if (full_seen) {
-        host = true;   // net/url.Parse
+      } else if (full_seen && !a.url_full) {
+        host = true;   // net/url.Parse (otlp_url_full: otlp_url_full_kernel.hip parses it behind this kernel)
       }
     }
     if (host) {

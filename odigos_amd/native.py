@@ -159,6 +159,7 @@ def lib() -> C.CDLL:
         "ose_host_free": (None, [_p]),
         "ose_otlp_columns": (C.POINTER(Columns), [_p]),
         "ose_otlp_host_spans": (C.c_uint32, [_p]),
+        "ose_otlp_url_full_counts": (C.c_int, [_p, C.POINTER(C.c_uint64)]),
         "ose_otlp_walk_info": (C.c_int, [_p, C.POINTER(C.c_uint32)]),
         "ose_otlp_timings": (C.c_int, [_p, C.POINTER(C.c_double)]),
         "ose_otlp_attrset": (C.c_int, [_p, C.c_uint32, C.c_char_p, C.c_size_t]),
@@ -293,6 +294,7 @@ def lib() -> C.CDLL:
                                                C.POINTER(C.c_int)]),
         "osehost_span_attr_eval": (C.c_int, [C.c_char_p, C.c_char_p]),
         "osehost_sqlop_detect": (C.c_uint32, [C.c_char_p, C.c_size_t]),
+        "osehost_url_full_parse": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32), _p]),
         "osehost_condattr_compile": (C.c_int, [C.c_char_p, C.POINTER(CondAttrInfo), C.POINTER(_p)]),
         "osehost_condattr_blob": (C.c_int, [C.c_char_p, C.POINTER(_p), C.POINTER(C.c_size_t)]),
         "osehost_condattr_span": (C.c_int, [C.c_char_p, C.POINTER(CondAttrColumns), C.POINTER(CondAttrOutputs)]),

@@ -32,6 +32,17 @@ whole-job spans/s only: their legs overlap and are not reported).  Writes
 profiles/otlp_condattr_bench.json unless --out names another file; an
 "option_off_ab" entry already in that file (the parent-commit comparison,
 made by a job of its own) is kept.  A record, not a gate.
+
+--url-full SHARE: the engine option otlp_url_full off against on, on one
+build and interleaved call by call.  That share of the mix's HTTP spans
+carries url.full alone (a scheme, a host, the same path, a query; a tenth of
+them with an escaped segment more), so with the option off they take the
+decoder's host pass.  8192-span requests (decode -> stages -> encode) from 1
+caller (each leg and the decode phases timed) and from 8 callers (whole-job
+spans/s), and one --spans message (default 1M here).  The entry of this SHARE
+in profiles/otlp_url_full_bench.json is replaced, the others and "parent_ab"
+(the parent-commit comparison, made by a job of its own) are kept.  A record,
+not a gate.
 """
 from __future__ import annotations
 
@@ -51,8 +62,16 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--sqlop", action="store_true", help="odigossqldboperationprocessor through the OTLP path")
     ap.add_argument("--condattr", action="store_true", help="odigosconditionalattributes through the OTLP path")
+    ap.add_argument("--url-full", type=float, default=None, metavar="SHARE",
+                    help="otlp_url_full off against on; SHARE of the HTTP spans carries url.full alone")
     ap.add_argument("--out", default=str(ROOT / "gpurun_out" / "otlp.json"))
     args = ap.parse_args()
+    if args.url_full is not None:
+        if args.out == ap.get_default("out"):
+            args.out = str(ROOT / "profiles" / "otlp_url_full_bench.json")
+        if args.spans == ap.get_default("spans"):
+            args.spans = 1_000_000
+        return url_full_main(args)
     if args.condattr:
         if args.out == ap.get_default("out"):
             args.out = str(ROOT / "profiles" / "otlp_condattr_bench.json")
@@ -443,6 +462,128 @@ def condattr_main(args):
             pass
     out.parent.mkdir(parents=True, exist_ok=True)
     out.write_text(json.dumps(res, indent=1) + "\n")
+    print(json.dumps(res), flush=True)
+
+
+def url_full_main(args):
+    import threading
+
+    import torch
+    from bench import NODE_KEYS, cpu_share
+    from odigos_amd import native
+    from odigos_amd.batch import Engine, Generator, OtlpBatch, PinnedBuffer, device_outputs
+    from tests.workloads import c3_sampling_config
+    share_cpu, nproc, model = cpu_share()
+    threads = max(1, min(16, share_cpu))
+    share = args.url_full
+    cfg = {"odigossampling": c3_sampling_config(), "odigosurltemplate": {},
+           "odigostrafficmetrics": {"res_attributes_keys": NODE_KEYS}}
+    engs = {"off": Engine(cfg), "on": Engine(cfg)}
+    engs["on"].set_option("otlp_url_full", 1)
+    st = native.STAGE_SAMPLE | native.STAGE_TEMPLATE | native.STAGE_SIZE
+    sh = torch.cuda.current_stream().cuda_stream
+    med = lambda xs: sorted(xs)[len(xs) // 2]   # noqa: E731
+
+    def message(n, seed):
+        pb = Generator("fused", seed=seed, n_spans=n, threads=threads).otlp(threads, url_full=share)
+        dims = native.Columns()
+        dims.n_spans, dims.n_resources, dims.n_attrsets = n, n, 4096
+        return pb, PinnedBuffer(pb), dims
+
+    def one(arm, pin, outs, stream, timed):
+        eng = engs[arm]
+        a = time.perf_counter()
+        ob = OtlpBatch(eng, pin.p, stream=stream, length=pin.n, outputs=outs)
+        b = time.perf_counter()
+        eng.process_device(ob, st, native.GROUP_TRACE_ID, seed=0x5EED, stream=stream)
+        if timed:
+            torch.cuda.synchronize()
+        c = time.perf_counter()
+        ob.encode(st, native.GROUP_TRACE_ID, None, stream=stream, copy=False)
+        d = time.perf_counter()
+        r = {"decode": (b - a) * 1e3, "stages": (c - b) * 1e3, "encode": (d - c) * 1e3, "total": (d - a) * 1e3,
+             "phases": ob.timings_ms, "host_spans": ob.host_spans, "counts": ob.url_full_counts}
+        ob.close()
+        return r
+
+    def summary(runs):
+        return {"decode_ms_median": med([r["decode"] for r in runs]), "decode_ms_min": min(r["decode"] for r in runs),
+                "total_ms_median": med([r["total"] for r in runs]),
+                "decode_phases_ms_median": {k: med([r["phases"][k] for r in runs]) for k in runs[0]["phases"]},
+                "host_pass_spans": runs[-1]["host_spans"], "url_full_counts": list(runs[-1]["counts"]), "calls": len(runs)}
+
+    res = {"metric": "ose_otlp_decode (and decode -> SAMPLE|TEMPLATE|SIZE -> ose_otlp_encode) with the engine option "
+                     "otlp_url_full off against on, arms interleaved on one build",
+           "url_full_share": share, "host_cpu": model, "cpu_share": share_cpu, "nproc": nproc}
+    # 8192-span requests, one caller: the arms alternate call by call
+    spb, spin, sdims = message(8192, 0x0D16F0A2)
+    souts = device_outputs(sdims, tmpl_cap=64 * 8192)
+    res["request8192_message_bytes"] = len(spb)
+    res["request8192_url_full_spans"] = spb.count(b"url.full")
+    runs = {"off": [], "on": []}
+    for k in range(240):
+        for arm in ("off", "on"):
+            r = one(arm, spin, souts, sh, True)
+            if k >= 40:
+                runs[arm].append(r)
+    res["request8192_1caller"] = {arm: summary(runs[arm]) for arm in runs}
+    # ... eight callers: whole-job spans/s, the arms in alternating blocks
+    callers, per = 8, 60
+    blocks = {"off": [], "on": []}
+    couts = [device_outputs(sdims, tmpl_cap=64 * 8192) for _ in range(callers)]
+    cstreams = [torch.cuda.Stream() for _ in range(callers)]
+    for blk in range(6):
+        arm = ("off", "on")[blk % 2]
+        ready = threading.Barrier(callers + 1)
+        errs = []
+
+        def caller(k):
+            try:
+                ready.wait()
+                for _ in range(per):
+                    one(arm, spin, couts[k], cstreams[k].cuda_stream, False)
+                cstreams[k].synchronize()
+            except Exception as ex:   # pragma: no cover
+                errs.append(repr(ex))
+                ready.abort()
+
+        th = [threading.Thread(target=caller, args=(k,)) for k in range(callers)]
+        for t_ in th:
+            t_.start()
+        ready.wait()
+        a = time.perf_counter()
+        for t_ in th:
+            t_.join()
+        wall = time.perf_counter() - a
+        assert not errs, errs
+        if blk >= 2:   # the first block of each arm warms the callers' buffers
+            blocks[arm].append(callers * per * 8192 / wall)
+    res["request8192_8callers_spans_per_s"] = {arm: {"blocks": v, "median": med(v)} for arm, v in blocks.items()}
+    spin.close()
+    # one large message: decode from pinned memory, the arms alternating
+    pb, pin, dims = message(args.spans, 0x0D16F0A1)
+    outs = device_outputs(dims, tmpl_cap=64 * args.spans)
+    res["message_spans"] = args.spans
+    res["message_bytes"] = len(pb)
+    res["message_url_full_spans"] = pb.count(b"url.full")
+    runs = {"off": [], "on": []}
+    for k in range(args.reps + 1):
+        for arm in ("off", "on"):
+            r = one(arm, pin, outs, sh, True)
+            if k >= 1:
+                runs[arm].append(r)
+    res["message"] = {arm: summary(runs[arm]) for arm in runs}
+    pin.close()
+    out = Path(args.out)
+    doc = {}
+    if out.exists():
+        try:
+            doc = json.loads(out.read_text())
+        except ValueError:
+            doc = {}
+    doc["share_%g" % share] = res
+    out.parent.mkdir(parents=True, exist_ok=True)
+    out.write_text(json.dumps(doc, indent=1) + "\n")
     print(json.dumps(res), flush=True)
 
 
